@@ -8,10 +8,16 @@ per GPU, each with its own shard (rank-seeded batch; rule tables replicated):
 weak scaling, no data-path collective.  Counters are reduced over RCCL once,
 after the timed region (reported separately as reduce_ms).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+A plain run sets up, warms up, times the steps, writes its outputs when
+--dump-outputs DIR is given, and prints ONE JSON line on rank 0 (contract in
+the task statement), including
   roofline:     algorithmic bytes per launch (sum over packets of
                 min(len,128)+1) / average kernel duration from
                 HIP events on the launch stream, vs the 8 TB/s HBM peak
+--full adds the legs that take runs of their own:
+  roofline.peak_measured_stream_read / frac_of_measured: the streaming-read
+                rate this device reaches over the same buffer
+  host_path:    the PCIe-inclusive rate of the same workload from host memory
   cpu_baseline: the CPU restatement of xdpfilt_dny_all (oracle/, "port")
                 with the reference's cost model (one hash probe per
                 CHECK_MAP, per-thread counters summed) on a bounded sample
@@ -77,14 +83,20 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2-packets", type=int, default=26)
     ap.add_argument("--rules", type=int, default=1_000_000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as "
+                         "DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the measured "
+                         "streaming-read peak, the host-memory path, the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="target CPU-baseline duration (0 disables)")
-    ap.add_argument("--no-cpu", action="store_true")
+                    help="--full: target CPU-baseline duration (0 disables)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--one-device", action="store_true",
                     help="rehearsal on a one-GPU box: every rank uses device 0 (RCCL then "
                          "refuses the shared device, which the line reports as reduce_error)")
     ap.add_argument("--host-log2-packets", type=int, default=22,
-                    help="sample for the PCIe-inclusive host-buffer rate (0 disables)")
+                    help="--full: sample for the PCIe-inclusive host-buffer rate (0 disables)")
     ap.add_argument("--rank-timeout", type=float, default=1800.0,
                     help="self-launch (--gpus N without a launcher): seconds before the "
                          "ranks count as stalled")
@@ -190,6 +202,11 @@ def main():
     st = f.stats(dev=0)
     assert int(st[:, 0].sum()) == n * (args.steps + args.warmup), st
 
+    # ---- the last step's outputs, as a caller of xfg_classify receives them
+    # (this rank's own, before the counters are summed over ranks)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, f, d_verd, n, v4, st)
+
     # ---- RCCL counter reduce (once, after the timed region)
     # (outside the timed region; a failure or a stall here is reported in the
     # line and never keeps the line from being printed)
@@ -208,15 +225,17 @@ def main():
 
         reduce_ms, reduce_err, reduce_stuck = watched_reduce(_reduce, args.reduce_timeout)
 
-    # ---- achievable streaming-read peak on this device (same 1 GiB buffer)
-    peak_meas_ms = f.stream_read_timed(d_data.ptr, n * stride, 5)
-    peak_meas = n * stride / (peak_meas_ms * 1e-3) / 1e9
+    # ---- --full: achievable streaming-read peak on this device (same buffer)
+    peak_meas = None
+    if args.full:
+        peak_meas_ms = f.stream_read_timed(d_data.ptr, n * stride, 5)
+        peak_meas = n * stride / (peak_meas_ms * 1e-3) / 1e9
 
-    # ---- PCIe-inclusive rate: the same workload handed over in host memory
-    # (xfg_classify_host: pinned staging, H2D, classify, D2H of verdicts);
-    # reported beside `value`, never as it
+    # ---- --full: PCIe-inclusive rate: the same workload handed over in host
+    # memory (xfg_classify_host: pinned staging, H2D, classify, D2H of
+    # verdicts); reported beside `value`, never as it
     host_path = None
-    if rank == 0 and args.host_log2_packets > 0:
+    if args.full and rank == 0 and args.host_log2_packets > 0:
         hn = 1 << args.host_log2_packets
         hdata, hlens = X.gen_workload(7, 3, hn, stride, v4=v4, ports=ports, dst_permille=500,
                                       port_permille=250, bad_permille=10)
@@ -246,9 +265,9 @@ def main():
                              "registered: the kernels read the caller's mapped pages in place)"}
         del hdata
 
-    # ---- CPU baseline (rank 0, N=1 only)
+    # ---- --full: CPU baseline (rank 0, N=1 only)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and args.cpu_seconds > 0:
         cpu = cpu_baseline(X, np, v4, ports, args.cpu_seconds)
 
     # ---- traffic: PMC bytes cannot be counted inside this timed process
@@ -295,13 +314,14 @@ def main():
             "kernel_ms": round(kern_ms, 4),
             "kernel": f"one classify pass: {kname} + xfg_log_count_kernel (hit-log counts), "
                       "HIP events on the launch stream",
-            "peak_measured_stream_read": round(peak_meas, 1),
-            "frac_of_measured": round(achieved / peak_meas, 4),
             "traffic_source": traffic_src,
         },
-        "cpu_baseline": cpu,
         "gen_seconds": round(gen_s, 2),
     }
+    if args.full:
+        line["roofline"]["peak_measured_stream_read"] = round(peak_meas, 1)
+        line["roofline"]["frac_of_measured"] = round(achieved / peak_meas, 4)
+        line["cpu_baseline"] = cpu
     if reduce_ms is not None:
         line["reduce_ms"] = round(reduce_ms, 3)
     if reduce_err is not None:
@@ -316,6 +336,50 @@ def main():
     f.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_LOG2 = 22    # verdicts dumped of a larger batch (16 MiB as float32)
+DUMP_SAMPLE_SEED = 0x5eed
+
+
+def dump_sample_index(np, n):
+    """The packets whose verdicts --dump-outputs writes: all of a batch of up
+    to 2^DUMP_SAMPLE_LOG2 packets, else a fixed scatter of that many distinct
+    indices (an odd multiplier modulo the power-of-two batch, offset by the
+    seed), in ascending order."""
+    m = 1 << DUMP_SAMPLE_LOG2
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    i = np.arange(m, dtype=np.uint64) * np.uint64(2654435761) + np.uint64(DUMP_SAMPLE_SEED)
+    return np.sort((i & np.uint64(n - 1)).astype(np.int64))
+
+
+def dump_outputs(out_dir, rank, f, d_verd, n, v4, st):
+    """What a caller of the timed path holds after the last timed step, as
+    out_dir/<name>.npy (rank r > 0: <name>_rank<r>.npy), about 25 MiB at the
+    default sizes:
+      verdicts          float32: the last launch's verdict bytes, at
+                        dump_sample_index() of the batch
+      verdict_counts    float64[256]: that launch's whole verdict buffer, tallied
+      stats             float64[actions, 2]: packets and bytes per action
+      ipv4_rule_hits    float64[rules]: hit counter of every IPv4 rule, rule order
+      port_values       float64[65536]: the port map's values
+    The counters are the context's own, so they run over the warm-up and the
+    timed steps together; the inputs are seeded, so the same arguments give
+    the same files."""
+    import numpy as np
+    import xfgpu as G
+    os.makedirs(out_dir, exist_ok=True)
+    verd = d_verd.download(np.empty(n, np.uint8))
+    hits = f.values_of(G.MAP_IPV4, v4, dev=0) >> np.uint64(6)
+    pvals = f.values_of(G.MAP_PORTS, np.arange(65536, dtype=np.uint32), dev=0)
+    sfx = f"_rank{rank}" if rank else ""
+    for name, arr in (("verdicts", verd[dump_sample_index(np, n)].astype(np.float32)),
+                      ("verdict_counts", np.bincount(verd, minlength=256).astype(np.float64)),
+                      ("stats", st.astype(np.float64)),
+                      ("ipv4_rule_hits", hits.astype(np.float64)),
+                      ("port_values", pvals.astype(np.float64))):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), arr)
 
 
 def watched_reduce(fn, timeout):

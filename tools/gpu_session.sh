@@ -19,7 +19,7 @@ if [[ $STEPS == all || $STEPS == *smoke* ]]; then
   [ $rc -eq 0 ] || exit $rc
 fi
 if [[ $STEPS == all || $STEPS == *bench* ]]; then
-  timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > "$OUT/bench_$TAG.log" 2>&1
+  timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench_$TAG.log" 2>&1
   rc=$?; echo "bench rc=$rc"; tail -3 "$OUT/bench_$TAG.log"
   [ $rc -eq 0 ] || exit $rc
 fi
