@@ -94,8 +94,15 @@ struct xfg_open_opts {
 	 * a 128-byte window per frame; a frame whose parse reaches past byte
 	 * 64 -- IPv6/TCP, long IPv6 extension chains, IPv4 options -- takes the
 	 * deferred walk over the whole frame), 128 => 128-byte windows.
-	 * Results never depend on it. */
+	 * Results never depend on it.  AF_XDP descriptor batches on the
+	 * pipelined kernel use the same window. */
 	uint32_t window;
+	uint32_t reserved0;      /* (the earlier layout's tail padding: ignored) */
+	/* AF_XDP descriptor batches (xfg_classify_descs) of at least this many
+	 * packets take the pipelined kernel, smaller ones the general kernel,
+	 * whose fixed cost per launch is lower: 0 => default (2^16), 1 => every
+	 * batch.  Results never depend on it. */
+	uint32_t descs_min_packets;
 };
 
 /*
@@ -117,8 +124,11 @@ int xfg_num_devices(const xfg_ctx *ctx);            /* analogue of libbpf_num_po
 const char *xfg_strerror(int err);
 
 /* The classify kernel the last launch on device @dev ran (introspection for
- * tests and tools): XFG_PATH_GENERAL (offsets, descriptors, header
- * windows), _PIPELINE (fixed stride, any live key), _IPV4 (IPv4 keys only:
+ * tests and tools): XFG_PATH_GENERAL (offsets, header windows, the
+ * descriptor batches of the Ethernet-only programs, those below
+ * xfg_open_opts.descs_min_packets and those of 2^32 packets or more),
+ * _PIPELINE (fixed stride with any live key; AF_XDP
+ * descriptors, xfg_classify_descs), _IPV4 (IPv4 keys only:
  * prefilter + bucket line), _QT (IPv4 keys only: the quotient index),
  * _ETH (the Ethernet-only programs, their map as an LDS key table); or
  * -EINVAL / -ENOENT (no launch yet). */
@@ -303,6 +313,11 @@ void xfg_host_free_pinned(void *p);
  * on that same stream (used by bench.py for the roofline figure). */
 int xfg_classify_timed(xfg_ctx *ctx, int dev, const struct xfg_batch *batch,
 		       uint8_t *verdicts, int iters, double *avg_ms);
+/* The same for a descriptor batch (xfg_classify_descs): @iters >= 1 launches
+ * between the two events, the hit log still pending counted inside the timed
+ * region.  -EINVAL for an empty batch. */
+int xfg_classify_descs_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
+			     uint8_t *verdicts, int iters, double *avg_ms);
 
 /* Streaming-read probe: average duration of a kernel that reads @bytes of
  * device memory at @src with 16-byte non-temporal loads (the achievable HBM

@@ -14,6 +14,14 @@
   c3e  C3 plus C1's 8 MAC rules (4 dst, 4 src; a ruled MAC in 10 % of the
       frames): Ethernet rules beside IP rules, the generic pipelined kernel
       with the Ethernet map as its LDS key table
+  c3d  C3's workload as an AF_XDP descriptor batch (xfg_classify_descs_timed):
+      the 64 B frames in a UMEM of 2 KiB chunks at headroom 256, chunks in
+      random order, read through an RX ring that wraps.  With the diagnostics
+      library (XFG_LIB=diag) also the same batch on the general kernel
+      (XFG_KERNEL=general: what a descriptor batch ran before the pipelined
+      descriptor mode) and, strided, on the generic pipelined kernel
+      (XFG_KERNEL=generic) and the quotient-index kernel.  2^22 packets by
+      default: an 8 GiB UMEM (the workload's 2^24 would need 32 GiB)
 
   c1  xdpfilt_alw_eth, the 8 MAC rules 02:00:00:00:00:0{1..8} (4 dst, 4
       src), 64 B Ethernet/IPv4/UDP frames, 25% carrying a ruled MAC (SURVEY.md
@@ -97,12 +105,102 @@ def run_c1(args):
     print(json.dumps(line), flush=True)
 
 
+C3D_CHUNK, C3D_HEADROOM = 2048, 256
+
+
+def run_c3d(args):
+    import numpy as np
+    import xftools as X
+    import xfgpu as G
+    n = 1 << (args.log2_packets or 22)
+    n4, nports, stride = 1_000_000, 16, 64
+    t0 = time.time()
+    v4 = X.rand_keys(3, int(n4 * 1.02) + 16, 4)[:n4]
+    ports = (np.arange(nports, dtype=np.uint32) * 61 + 53).astype(np.uint16)
+    data, lens = X.gen_workload(3, 3, n, stride, v4=v4, ports=ports)
+    # (descs_min_packets=1: the pipelined descriptor mode at any --log2-packets,
+    # also below the size from which xfg_classify_descs takes it by default)
+    f = G.Filter(G.FEAT_ALL | G.FEAT_DENY, devices=[0], ipv4_capacity=n4, ipv6_capacity=1024,
+                 descs_min_packets=1)
+    f.update_batch(G.MAP_IPV4, v4, np.full(len(v4), 2, np.uint64))
+    pk = np.array([X.port_key(int(p)) for p in ports], "<u4").view(np.uint8)
+    f.update_batch(G.MAP_PORTS, pk, np.full(len(ports), 2 | 4 | 8, np.uint64))
+    # frame i in chunk perm[i]; the UMEM is built and uploaded a piece at a
+    # time (chunk c holds frame inv[c])
+    rng = np.random.default_rng(12)
+    perm = rng.permutation(n)
+    inv = np.empty(n, np.int64)
+    inv[perm] = np.arange(n)
+    d_umem = f.alloc(n * C3D_CHUNK)
+    frames = data.reshape(n, stride)
+    piece = 1 << 17
+    buf = np.zeros((piece, C3D_CHUNK), np.uint8)
+    for c0 in range(0, n, piece):
+        c1 = min(n, c0 + piece)
+        buf[:c1 - c0, C3D_HEADROOM:C3D_HEADROOM + stride] = frames[inv[c0:c1]]
+        G._check(G.lib.xfg_memcpy_h2d(f.ctx, 0, d_umem.ptr + c0 * C3D_CHUNK, buf.ctypes.data,
+                                      (c1 - c0) * C3D_CHUNK), "memcpy_h2d")
+    # the RX ring: twice the batch, the batch starting 777 before its end
+    entries = 2 * n
+    first = entries - 777
+    descs = np.zeros((entries, 2), np.uint64)
+    idx = (first + np.arange(n)) & (entries - 1)
+    descs[idx, 0] = perm.astype(np.uint64) * np.uint64(C3D_CHUNK) + np.uint64(C3D_HEADROOM)
+    descs[idx, 1] = lens.astype(np.uint64)
+    d_descs, d_verd = f.alloc(descs.nbytes), f.alloc(n)
+    d_descs.upload(descs)
+    setup_s = time.time() - t0
+    print(f"[c3d] set up {setup_s:.1f}s", file=sys.stderr, flush=True)
+
+    def descs_ms():
+        a = (d_umem.ptr, d_descs.ptr, n, d_verd.ptr)
+        f.classify_descs_timed(*a, 2, first=first, mask=entries - 1)
+        return f.classify_descs_timed(*a, args.iters, first=first, mask=entries - 1), f.last_path()
+
+    def mpps(ms):
+        return round(n / (ms * 1e-3) / 1e6, 1)
+
+    runs = max(1, args.runs)
+    new = [descs_ms() for _ in range(runs)]
+    line = {"config": "c3d", "program": f.prog_name, "packets": n, "umem_chunk": C3D_CHUNK,
+            "headroom": C3D_HEADROOM, "ring_entries": entries, "rules_ipv4": n4,
+            "port_rules": nports, "kernel_path": new[0][1],
+            "kernel_ms": [round(m, 4) for m, _ in new], "Mpps": [mpps(m) for m, _ in new],
+            "setup_s": round(setup_s, 1)}
+    if os.environ.get("XFG_LIB") == "diag":
+        # the diagnostics library reads its knobs at every launch
+        os.environ["XFG_KERNEL"] = "general"
+        old = [descs_ms() for _ in range(runs)]
+        del os.environ["XFG_KERNEL"]
+        line["general"] = {"kernel_path": old[0][1], "kernel_ms": [round(m, 4) for m, _ in old],
+                           "Mpps": [mpps(m) for m, _ in old]}
+        line["speedup_vs_general"] = round(min(m for m, _ in old) / min(m for m, _ in new), 3)
+        # the same frames as a strided batch: the generic pipelined kernel
+        # (key mode 0) and the kernel C3 runs (the quotient index)
+        d_data, d_lens = f.alloc(data.nbytes), f.alloc(lens.nbytes)
+        d_data.upload(data)
+        d_lens.upload(lens)
+        for key, knob in (("strided_generic", "generic"), ("strided_qt", None)):
+            if knob:
+                os.environ["XFG_KERNEL"] = knob
+            f.classify_timed(d_data.ptr, d_lens.ptr, n, stride, d_verd.ptr, 2)
+            ms = [f.classify_timed(d_data.ptr, d_lens.ptr, n, stride, d_verd.ptr, args.iters)
+                  for _ in range(runs)]
+            line[key] = {"kernel_path": f.last_path(), "kernel_ms": [round(m, 4) for m in ms],
+                         "Mpps": [mpps(m) for m in ms]}
+            os.environ.pop("XFG_KERNEL", None)
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
 def run(name, args):
     import numpy as np
     import xftools as X
     import xfgpu as G
     if name == "c1":
         return run_c1(args)
+    if name == "c3d":
+        return run_c3d(args)
     kind = {"c2": 2, "c3": 3, "c4": 4, "c5": 5, "c3sd": 3, "c3e": 3}[name]
     n = 1 << (args.log2_packets or {"c2": 24, "c3": 24, "c4": 23, "c5": 23, "c3sd": 24, "c3e": 24}[name])
     stride = 64 if kind in (2, 3) else 1536
@@ -191,7 +289,10 @@ def run(name, args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("configs", nargs="*", default=["c2", "c4", "c5", "c3sd"])
-    ap.add_argument("--log2-packets", type=int, default=0)
+    ap.add_argument("--log2-packets", type=int, default=0,
+                    help="batch size (c3d: 22 by default, an 8 GiB UMEM of 2 KiB chunks; "
+                         "the workload's 2^24 would need 32 GiB beside the other buffers)")
+    ap.add_argument("--runs", type=int, default=3, help="c3d: timed runs of each leg")
     ap.add_argument("--no-cpu", action="store_true", help="c1: the GPU leg only")
     ap.add_argument("--no-host", action="store_true",
                     help="c5: the device-resident leg only (PMC passes of its kernel)")

@@ -45,6 +45,11 @@ int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 
 #define NMAPS_HASH 3 /* ipv4, ipv6, ethernet */
 #define XFG_HOST_REG_MAX 16 /* registered host buffers per context */
+/* kernel kinds of the occupancy table (xfg_dev.occ, xfg_classify_occupancy);
+ * XFG_OCC_DESCS: the generic pipelined kernel's descriptor instantiation --
+ * a kind-1 launch (XFG_PATH_PIPELINE) whose grid is sized from its own entry */
+#define XFG_OCC_KINDS 9
+#define XFG_OCC_DESCS 8
 /* host-resident classify: staging slots in flight (each: a chunk's copies,
  * kernel and verdicts on its own stream; the host prepares the next chunk
  * while the others move) */
@@ -83,9 +88,10 @@ struct xfg_dev {
 	 * 5 pipelined IPv4-key mode over the quotient index, 6 Ethernet-key]
 	 * [window 64, 128][dynamic LDS: none, direct counters, port nibble map,
 	 * both] */
-	int occ[8][2][16];  /* [..][dynamic LDS: + bit 2, the Bloom words (bl_lds);
+	int occ[XFG_OCC_KINDS][2][16];  /* [..][dynamic LDS: + bit 2, the Bloom words (bl_lds);
 			     * + bit 3, the LDS Ethernet key table (xfg_kargs.ek)]; kind 7:
-			     * kind 5 with its count wave (0: cannot launch) */
+			     * kind 5 with its count wave (0: cannot launch); kind 8
+			     * (XFG_OCC_DESCS): kind 1's descriptor instantiation */
 	/* the Ethernet-key kernel's key table (kind 6), uploaded from ctx->ek
 	 * when ek_gen falls behind ctx->ek_gen; params read at launch under
 	 * d->lock */
@@ -181,6 +187,7 @@ struct xfg_ctx {
 	uint32_t ek_gen;              /* tables built (0: none yet) */
 	int ek_ok;
 	uint32_t qt_min_keys;
+	uint32_t descs_min;          /* descriptor batches from this size: the pipelined kernel */
 	uint32_t window;                /* header window above a 64-byte stride: 64 or 128 */
 	uint32_t port_flag_cnt[8];
 	/* multi-process reduction */
@@ -196,6 +203,13 @@ struct xfg_ctx {
 /* Default smallest IPv4 map that takes the quotient index (its 2^17 buckets
  * are 4 MiB: below this the canonical table and its prefilter stay in L2). */
 #define XFG_QT_MIN_KEYS (1u << 18)
+/* AF_XDP descriptor batches below this many packets keep the general kernel
+ * (xfg_open_opts.descs_min_packets overrides it): on C3's workload as a
+ * descriptor batch the pipelined descriptor mode costs 16.7-17.5 us a launch
+ * up to 2^16 packets, the general kernel 13.9-14.3 us up to 2^15 and
+ * 16.9-17.5 at 2^16; from 2^17 the pipelined mode is ahead (19.1 against
+ * 23.5 us; 1.28x at 2^18, 1.79x at 2^22) -- profiles/r07_c3d_ab.log */
+#define XFG_DESCS_PIPE_MIN (1u << 16)
 #define XFG_LOG_PEND_MAX 4u   /* quotient-index launches per count kernel */
 
 /* ------------------------------------------------------------------ misc */
@@ -510,7 +524,7 @@ static int dev_init(xfg_ctx *ctx, struct xfg_dev *d)
 	HIPCHK(hipEventCreateWithFlags(&d->ev_user, hipEventDisableTiming));
 	HIPCHK(hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming));
 
-	for (int k = 0; k < 8; k++)
+	for (int k = 0; k < XFG_OCC_KINDS; k++)
 		for (int w = 0; w < 2; w++)
 			for (int c = 0; c < 16; c++)
 				d->occ[k][w][c] = xfg_classify_occupancy(
@@ -548,6 +562,10 @@ int xfg_open(xfg_ctx **out, const struct xfg_open_opts *opts)
 	ctx->qt_min_keys = XFG_QT_MIN_KEYS;
 	if (opts->sz >= offsetof(struct xfg_open_opts, qt_min_keys) + sizeof(uint32_t) && opts->qt_min_keys)
 		ctx->qt_min_keys = opts->qt_min_keys;
+	ctx->descs_min = XFG_DESCS_PIPE_MIN;
+	if (opts->sz >= offsetof(struct xfg_open_opts, descs_min_packets) + sizeof(uint32_t) &&
+	    opts->descs_min_packets)
+		ctx->descs_min = opts->descs_min_packets;
 	ctx->window = 64;
 	if (opts->sz >= offsetof(struct xfg_open_opts, window) + sizeof(uint32_t) && opts->window) {
 		if (opts->window != 64 && opts->window != 128) {
@@ -1523,8 +1541,10 @@ static int ek_refresh(xfg_ctx *ctx, struct xfg_dev *d)
 	return err;
 }
 
-static int fill_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b,
-		      uint8_t *verdicts, struct xfg_kargs *a)
+/* @db: the AF_XDP descriptors of the batch (xfg_classify_descs: @b then
+ * carries the UMEM and the count, no lengths and no stride), or NULL */
+static int fill_kargs_src(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b,
+			  const struct xfg_desc_batch *db, uint8_t *verdicts, struct xfg_kargs *a)
 {
 	memset(a, 0, sizeof(*a));
 	int err = port_tab_refresh(d);
@@ -1577,23 +1597,51 @@ static int fill_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b
 	 * indices fit its 32-bit deferred lists); the general kernel the rest. */
 	a->pipe = !b->offsets && b->stride >= a->window && !(b->stride & 15) &&
 		  !((uintptr_t)b->data & 15) && b->count < (1ull << 32) && b->stride < 65536;
+	const int ek_only = !(ctx->prog_features & (XFG_FEAT_IPV4 | XFG_FEAT_IPV6 | XFG_FEAT_TCP | XFG_FEAT_UDP));
+	if (db) {
+		/* AF_XDP descriptors: the generic pipelined kernel's descriptor
+		 * mode (xfg_pipeline.hip, SRC_DESCS; 32-bit packet indices) with the
+		 * context's window -- and no other pipelined kernel: key mode 0
+		 * whatever the census says, no quotient index (below).  The
+		 * Ethernet-only programs' pipelined kernel is the Ethernet-key one,
+		 * which reads fixed-stride slots: their descriptor batches keep the
+		 * general kernel, with the 128-byte window it always had there; so
+		 * do batches below XFG_DESCS_PIPE_MIN packets (above: the
+		 * general kernel's lower fixed cost wins there). */
+		a->descs = db->descs;
+		a->desc_mask = db->mask;
+		a->desc_first = db->first;
+		a->pipe = !ek_only && b->count < (1ull << 32) && b->count >= ctx->descs_min;
+	}
 #ifdef XFG_DIAG
 	const char *ks = getenv("XFG_KERNEL");   /* diagnostics build only */
 	if (ks && !strcmp(ks, "general"))
 		a->pipe = 0;
 #endif
+	if (db)
+		a->window = a->pipe ? ctx->window : 128;
 	a->dense = a->pipe && a->stride == a->window;
 	/* key mode 1: no Ethernet or IPv6 lookup can hit (flag census), so the
 	 * pipelined kernel carries IPv4 keys only */
 	int eth_live = (ctx->prog_features & XFG_FEAT_ETHERNET) && a->te.count && (a->te.fmask & 3);
 	int v6_live = (ctx->prog_features & XFG_FEAT_IPV6) && a->t6.count && (a->t6.fmask & 3);
-	a->km = (ctx->prog_features & XFG_FEAT_IPV4) && !eth_live && !v6_live;
+	a->km = !db && (ctx->prog_features & XFG_FEAT_IPV4) && !eth_live && !v6_live;
 	/* (IPv6 keys live, Ethernet keys not: the quotient-index kernel may still
 	 * take the batch, sending every IPv6 frame to its deferred path) */
-	const int km6 = (ctx->prog_features & XFG_FEAT_IPV4) && !eth_live && v6_live;
+	const int km6 = !db && (ctx->prog_features & XFG_FEAT_IPV4) && !eth_live && v6_live;
 	a->v6d = 0;
-	/* per-lane u32 byte sums in the pipelined kernel: bound them */
-	if (a->pipe && (uint64_t)a->stride * (((b->count + 63) / 64 + 1023) / 1024 + 1) >= (1ull << 32))
+	int kgen = 0;
+#ifdef XFG_DIAG
+	/* "generic": key mode 0 whatever the census says -- the generic
+	 * pipelined kernel on a batch the IPv4-key kernels would take (the
+	 * strided figure beside a descriptor batch's, tools/bench_configs.py c3d) */
+	kgen = ks && !strcmp(ks, "generic");
+	if (kgen)
+		a->km = 0;
+#endif
+	/* per-lane u32 byte sums in the pipelined kernel: bound them (the
+	 * descriptor mode sums in 64 bits: its lengths are not the host's to see) */
+	if (!db && a->pipe && (uint64_t)a->stride * (((b->count + 63) / 64 + 1023) / 1024 + 1) >= (1ull << 32))
 		a->pipe = 0;
 #ifdef XFG_DIAG
 	const char *dm = getenv("XFG_DIAG_MASK");   /* pipelined IPv4-key kernel: drop a cost */
@@ -1604,7 +1652,7 @@ static int fill_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b
 		a->tstamp = (unsigned long long *)(uintptr_t)strtoull(tsp, NULL, 0);
 	const char *kk = getenv("XFG_KERNEL");   /* "split": parse + lookup passes */
 	if (kk && !strcmp(kk, "split"))
-		a->split = a->pipe && a->km;
+		a->split = a->pipe && a->km;   /* (km 0 with descriptors: never) */
 	const char *bo = getenv("XFG_BLOOM");    /* "off": lookup pass without the prefilter */
 	if (bo && !strcmp(bo, "off") && !(a->t4.count && (a->t4.fmask & 3) == 3))
 		a->bloom_off = 1;
@@ -1620,7 +1668,6 @@ static int fill_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b
 	/* (and, since round 6, for the generic pipelined kernel -- live
 	 * Ethernet keys beside IP keys: dny_all / alw_all with a few MAC rules --
 	 * which answers both Ethernet lookups from the same table in LDS) */
-	const int ek_only = !(ctx->prog_features & (XFG_FEAT_IPV4 | XFG_FEAT_IPV6 | XFG_FEAT_TCP | XFG_FEAT_UDP));
 	int ek = a->pipe && (ctx->prog_features & XFG_FEAT_ETHERNET) && (ek_only || eth_live);
 #ifdef XFG_DIAG
 	const char *eo = getenv("XFG_EK");   /* "off": the generic pipelined kernel */
@@ -1637,12 +1684,12 @@ static int fill_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b
 	 * table: the quotient-index kernel answers the Ethernet lookups from
 	 * the table ahead of its IPv4 lookups -- since round 6; else the
 	 * generic pipelined kernel takes the batch) */
-	const int kme = (ctx->prog_features & XFG_FEAT_IPV4) && eth_live && !v6_live && a->ek && !ek_only;
+	const int kme = !db && (ctx->prog_features & XFG_FEAT_IPV4) && eth_live && !v6_live && a->ek && !ek_only;
 	/* the quotient index (kind 5 kernel): the IPv4-key kernel with one or
 	 * both IPv4 lookup directions live, the same flags on every device, and
 	 * a map large enough that the prefilter + bucket-line chain leaves L2;
 	 * its hit log must fit the count kernel's histogram */
-	if (a->pipe && (a->km || km6 || kme) && !a->split) {
+	if (a->pipe && !kgen && (a->km || km6 || kme) && !a->split) {
 		/* (both directions live: up to two images, twice the QT slots) */
 		const int dl = a->t4.count && (a->t4.fmask & 2), sl = a->t4.count && (a->t4.fmask & 1);
 		const int ok = (dl | sl) && !ctx->flag_cnt[0][7] &&
@@ -1668,6 +1715,12 @@ static int fill_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b
 		}
 	}
 	return 0;
+}
+
+static int fill_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b,
+		      uint8_t *verdicts, struct xfg_kargs *a)
+{
+	return fill_kargs_src(ctx, d, b, NULL, verdicts, a);
 }
 
 /* Device scratch buffer of at least @bytes (grown on demand; the old one may
@@ -1832,7 +1885,8 @@ static int launch_batch(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_kargs 
 		a.qt_hits = d->qt_hits;
 		a.qt_hitx = d->qt_hits + d->qt_n;
 	}
-	int per_cu = d->occ[kind][wi][(a.dcnt > 0) | (!a.port_tab && a.port_count ? 2 : 0) |
+	/* (the descriptor instantiation of kind 1: its own occupancy entry) */
+	int per_cu = d->occ[kind == 1 && a.descs ? XFG_OCC_DESCS : kind][wi][(a.dcnt > 0) | (!a.port_tab && a.port_count ? 2 : 0) |
 				     (a.bl_lds ? 4 : 0) | (a.ek ? 8 : 0)];
 #ifdef XFG_DIAG
 	const char *g = getenv("XFG_GRID_PER_CU");
@@ -2110,8 +2164,8 @@ int xfg_classify(xfg_ctx *ctx, int dev, const struct xfg_batch *b, uint8_t *verd
 	return err;
 }
 
-int xfg_classify_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
-		       uint8_t *verdicts, void *stream)
+/* argument checks of the descriptor entry points; 1: an empty batch */
+static int check_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db, const void *verdicts)
 {
 	if (!ctx || !db || (!verdicts && db->count))
 		return -EINVAL;
@@ -2120,28 +2174,55 @@ int xfg_classify_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
 	if (dev < 0 || dev >= ctx->ndev)
 		return -EINVAL;
 	if (!db->count)
-		return 0;
+		return 1;
 	if (!db->umem || !db->descs || ((uintptr_t)db->descs & 7) || (db->mask & (db->mask + 1u)))
 		return -EINVAL;
-	struct xfg_dev *d = &ctx->dev[dev];
+	return 0;
+}
+
+static int descs_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_desc_batch *db,
+		       uint8_t *verdicts, struct xfg_kargs *a)
+{
 	struct xfg_batch b = { db->umem, NULL, NULL, db->count, 0, 0 };
-	struct xfg_kargs a;
 	pthread_mutex_lock(&ctx->lock);
 	ctx->reduced = 0;
-	int err = fill_kargs(ctx, d, &b, verdicts, &a);
+	int err = fill_kargs_src(ctx, d, &b, db, verdicts, a);
 	pthread_mutex_unlock(&ctx->lock);
+	return err;
+}
+
+int xfg_classify_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+		       uint8_t *verdicts, void *stream)
+{
+	int err = check_descs(ctx, dev, db, verdicts);
 	if (err)
+		return err < 0 ? err : 0;
+	struct xfg_dev *d = &ctx->dev[dev];
+	struct xfg_kargs a;
+	if ((err = descs_kargs(ctx, d, db, verdicts, &a)))
 		return err;
-	a.descs = db->descs;
-	a.desc_mask = db->mask;
-	a.desc_first = db->first;
-	a.window = 128;
-	a.pipe = 0;
-	a.dense = 0;
 	err = hip_err(hipSetDevice(d->ordinal));
 	if (!err)
 		err = launch_batch(ctx, d, &a, stream, 1);
 	return err;
+}
+
+static int timed_launches(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_kargs *a, int iters,
+			  double *avg_ms);
+
+int xfg_classify_descs_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+			     uint8_t *verdicts, int iters, double *avg_ms)
+{
+	int err = check_descs(ctx, dev, db, verdicts);
+	if (err < 0)
+		return err;
+	if (iters < 1 || !avg_ms || err)   /* (an empty batch has no time) */
+		return -EINVAL;
+	struct xfg_dev *d = &ctx->dev[dev];
+	struct xfg_kargs a;
+	if ((err = descs_kargs(ctx, d, db, verdicts, &a)))
+		return err;
+	return timed_launches(ctx, d, &a, iters, avg_ms);
 }
 
 int xfg_classify_timed(xfg_ctx *ctx, int dev, const struct xfg_batch *b, uint8_t *verdicts,
@@ -2154,16 +2235,25 @@ int xfg_classify_timed(xfg_ctx *ctx, int dev, const struct xfg_batch *b, uint8_t
 		return -EINVAL;
 	struct xfg_dev *d = &ctx->dev[dev];
 	struct xfg_kargs a;
-	float ms = 0;
 	pthread_mutex_lock(&ctx->lock);
 	ctx->reduced = 0;
 	err = fill_kargs(ctx, d, b, verdicts, &a);
 	pthread_mutex_unlock(&ctx->lock);
 	if (err)
 		return err;
+	return timed_launches(ctx, d, &a, iters, avg_ms);
+}
+
+/* @iters launches of one batch between two events on the device's stream
+ * (xfg_classify_timed, xfg_classify_descs_timed) */
+static int timed_launches(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_kargs *a, int iters,
+			  double *avg_ms)
+{
+	int err;
+	float ms = 0;
 	HIPCHK(hipSetDevice(d->ordinal));
 	HIPCHK(hipEventRecord(d->ev0, d->stream));
-	if ((err = launch_batch(ctx, d, &a, NULL, iters)))
+	if ((err = launch_batch(ctx, d, a, NULL, iters)))
 		goto fail;
 	/* (the logs still pending are counted inside the timed region: the
 	 * iterations' work is complete when ev1 fires) */

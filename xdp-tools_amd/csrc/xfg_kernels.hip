@@ -1634,7 +1634,19 @@ hipError_t launch_feat(const xfg_kargs &a, unsigned grid, hipStream_t s)
 	const size_t dl = (size_t)a.dcnt * 4 + (size_t)a.bl_lds * 4 +
 			  (a.port_nib && !a.port_tab && a.port_count ? XFG_PORT_NIB_WORDS * 4 : 0) +
 			  (a.ek ? 12 + (size_t)a.ek_slots * 16 : 0);   // (+ the table's alignment)
-	if (a.pipe) {
+	if (a.pipe && a.descs) {
+		// the AF_XDP descriptor batches the host routes to a pipelined
+		// kernel (not all: small ones, the Ethernet-only programs' and
+		// those of 2^32 packets or more come with pipe 0, xfg_ctx.c): the
+		// generic pipelined kernel's descriptor mode, key mode 0, and no
+		// other pipelined kernel (anything else is refused, never run)
+		if (a.km || a.qt || a.split || a.dense)
+			return hipErrorInvalidValue;
+		if (a.window <= 64)
+			hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 64, SRC_DESCS, 0>), dim3(grid), dim3(PIPE_THREADS(64)), dl, s, a);
+		else
+			hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 128, SRC_DESCS, 0>), dim3(grid), dim3(PIPE_THREADS(128)), dl, s, a);
+	} else if (a.pipe) {
 		bool done = false;
 		if constexpr ((FEAT & F_ETH) != 0 && (FEAT & (F_IPV4 | F_IPV6 | F_TCP | F_UDP)) == 0) {
 			// the Ethernet-only programs with their map as an LDS key table
@@ -1688,13 +1700,13 @@ hipError_t launch_feat(const xfg_kargs &a, unsigned grid, hipStream_t s)
 		}
 		if (!done) {
 			if (a.window <= 64 && a.dense)
-				hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 64, true, 0>), dim3(grid), dim3(PIPE_THREADS(64)), dl, s, a);
+				hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 64, SRC_DENSE, 0>), dim3(grid), dim3(PIPE_THREADS(64)), dl, s, a);
 			else if (a.window <= 64)
-				hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 64, false, 0>), dim3(grid), dim3(PIPE_THREADS(64)), dl, s, a);
+				hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 64, SRC_STRIDED, 0>), dim3(grid), dim3(PIPE_THREADS(64)), dl, s, a);
 			else if (a.dense)
-				hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 128, true, 0>), dim3(grid), dim3(PIPE_THREADS(128)), dl, s, a);
+				hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 128, SRC_DENSE, 0>), dim3(grid), dim3(PIPE_THREADS(128)), dl, s, a);
 			else
-				hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 128, false, 0>), dim3(grid), dim3(PIPE_THREADS(128)), dl, s, a);
+				hipLaunchKernelGGL((xfg_pipeline_kernel<FEAT, 128, SRC_STRIDED, 0>), dim3(grid), dim3(PIPE_THREADS(128)), dl, s, a);
 		}
 	} else if (a.window <= 64) {
 		hipLaunchKernelGGL((xfg_classify_kernel<FEAT, 64>), dim3(grid), dim3(TILE), dl, s, a);
@@ -1854,7 +1866,8 @@ static int occupancy_qt(uint32_t window, size_t dyn, hipError_t &e)
 // with `dyn` bytes of dynamic LDS: kind 0 = general, 1 = pipelined (key
 // mode 0), 2 = pipelined (key mode 1), 5 = pipelined over the quotient
 // index, 6 = the Ethernet-key kernel, 7 = kind 5 with its count wave (0:
-// it cannot launch); window 64 or 128.
+// it cannot launch), 8 = kind 1 over AF_XDP descriptors (its own
+// instantiation: its registers differ); window 64 or 128.
 template <uint32_t FEAT>
 static int occupancy_feat(int kind, uint32_t window, size_t dyn)
 {
@@ -1901,10 +1914,14 @@ static int occupancy_feat(int kind, uint32_t window, size_t dyn)
 		;
 	else if (kind == 6)
 		n = 1;   // (no such kernel for this program: never launched)
+	else if (kind == 8)   // the generic pipelined kernel's descriptor mode
+		e = window <= 64
+			? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xfg_pipeline_kernel<FEAT, 64, SRC_DESCS, 0>, PIPE_THREADS(64), dyn)
+			: hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xfg_pipeline_kernel<FEAT, 128, SRC_DESCS, 0>, PIPE_THREADS(128), dyn);
 	else if (kind >= 1)
 		e = window <= 64
-			? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xfg_pipeline_kernel<FEAT, 64, true, 0>, PIPE_THREADS(64), dyn)
-			: hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xfg_pipeline_kernel<FEAT, 128, false, 0>, PIPE_THREADS(128), dyn);
+			? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xfg_pipeline_kernel<FEAT, 64, SRC_DENSE, 0>, PIPE_THREADS(64), dyn)
+			: hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xfg_pipeline_kernel<FEAT, 128, SRC_STRIDED, 0>, PIPE_THREADS(128), dyn);
 	else
 		e = window <= 64
 			? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xfg_classify_kernel<FEAT, 64>, TILE, dyn)

@@ -26,10 +26,23 @@
 //           point and the port stage, which LDS answers) and issue the Bloom
 //           words of the live keys
 //   L       tile k-1's candidate bucket lines issued
+//   D(k+2)  descriptor batches only (SRC_DESCS): each lane's xdp_desc record
+//           of tile k+2 issued -- it has arrived at the next iteration's
+//           wait, whose stage S issues tile k+2's windows from it
 //
 // Nothing loaded in an iteration is used before the next one: the one wait
 // (an explicit vmcnt(0) at the top) is for loads in flight a whole
 // iteration.
+//
+// The batch layout is a template parameter (SRC): fixed-stride slots, dense
+// windows (stride == window), or AF_XDP descriptors over a UMEM
+// (xfg_classify_descs).  A descriptor names its frame's address and length,
+// so that mode has one more hop ahead of the windows (stage D), fetches a
+// packet's base from the lane that holds its record (window chunk c of the
+// tile belongs to packet c / CPP), loads only the chunks that start inside
+// the frame (the ABI promises no byte past the next 16-byte boundary after
+// its end: the rest of the window reads as zero) and takes every length from
+// the record: nothing in it derives from a stride.
 //
 // Whatever would need a further dependent hop, or a byte walk, inside an
 // iteration -- a shape the static-offset parse does not cover (VLAN tags,
@@ -47,6 +60,8 @@ namespace {
 
 constexpr uint32_t K_ETH = 1, K_V4 = 2, K_V6 = 3;
 constexpr uint32_t A_DEFER = 6;
+// batch layout of xfg_pipeline_kernel (SRC)
+constexpr int SRC_STRIDED = 0, SRC_DENSE = 1, SRC_DESCS = 2;
 
 #define PIPE_WAVES(W) ((W) <= 64 ? 8 : 4)
 #define PIPE_THREADS(W) (64 * PIPE_WAVES(W))
@@ -101,6 +116,9 @@ struct PktL {
 // near it would degrade to vmcnt(0).
 typedef const __attribute__((address_space(1))) uint32_t gu32;
 typedef const __attribute__((address_space(1))) u32x4 gu32x4;
+// (an xdp_desc record: the ring is only promised 8-byte alignment)
+typedef u32x4 __attribute__((aligned(8))) u32x4_a8;
+typedef const __attribute__((address_space(1))) u32x4_a8 gdesc;
 
 __device__ __forceinline__ uint32_t gload32(uint64_t addr)
 {
@@ -449,9 +467,11 @@ __device__ __forceinline__ void plan_packet(const xfg_kargs &a, const PktL<W> &p
 	}
 }
 
-template <uint32_t FEAT, int W, bool DENSE, int KM>
+template <uint32_t FEAT, int W, int SRC, int KM>
 __global__ __launch_bounds__(PIPE_THREADS(W), (W) <= 64 ? 4 : 2) void xfg_pipeline_kernel(const xfg_kargs a)
 {
+	constexpr bool DENSE = SRC == SRC_DENSE, DESC = SRC == SRC_DESCS;
+	static_assert(!DESC || KM == 0, "descriptor batches: key mode 0 only");
 	constexpr int NW = PIPE_WAVES(W);
 	constexpr int NT = 64 * NW;
 	constexpr int PK = KM == 1 ? 2 : 4;     // live hash keys carried per packet
@@ -528,8 +548,12 @@ __global__ __launch_bounds__(PIPE_THREADS(W), (W) <= 64 ? 4 : 2) void xfg_pipeli
 	const uint32_t nt = (n + 63) / 64;
 	const uint32_t first = blockIdx.x * NW + wv;
 	const uint32_t step = gridDim.x * NW;
-	// per-lane stats (u32: the host bounds a lane's byte sum below 2^32)
-	uint32_t st_c0 = 0, st_c1 = 0, st_c2 = 0, st_b0 = 0, st_b1 = 0, st_b2 = 0;
+	// per-lane stats (u32: the host bounds a lane's byte sum below 2^32 from
+	// the stride; descriptor lengths live in device memory, where the host
+	// cannot bound them: there the byte sums are 64-bit)
+	using bsum_t = std::conditional_t<DESC, uint64_t, uint32_t>;
+	uint32_t st_c0 = 0, st_c1 = 0, st_c2 = 0;
+	bsum_t st_b0 = 0, st_b1 = 0, st_b2 = 0;
 	auto stat = [&](uint32_t act, uint32_t len) {
 		st_c0 += act == A_ABORTED;
 		st_c1 += act == A_DROP;
@@ -544,9 +568,47 @@ __global__ __launch_bounds__(PIPE_THREADS(W), (W) <= 64 ? 4 : 2) void xfg_pipeli
 	// stride: the slot is the frame's buffer)
 	u32x4 pre[CPP];
 	uint32_t plen = 0;
+	// D: the lane's descriptor of a tile {addr lo, addr hi, len, options};
+	// lanes past the batch's end load nothing (the ring beyond it may be
+	// uninitialised) and keep a zero record
+	[[maybe_unused]] u32x4 dsc = { 0, 0, 0, 0 };
+	[[maybe_unused]] auto load_desc = [&](uint32_t t) {
+		const uint32_t i = t * 64 + lane;
+		dsc = u32x4{ 0, 0, 0, 0 };
+		if (i < n)   // (indexed as desc_word())
+			dsc = *reinterpret_cast<gdesc *>((uint64_t)(uintptr_t)a.descs +
+							 16ull * ((a.desc_first + i) & a.desc_mask));
+	};
 	auto issue = [&](uint32_t t) {
 		const uint32_t base = t * 64;
 		const uint32_t rem = n - base >= 64 ? 64u : n - base;
+		if constexpr (DESC) {
+			// the frame of the lane's record, xsk_umem__add_offset_to_addr():
+			// umem + (addr & (2^48 - 1)) + (addr >> 48); a chunk's packet
+			// sits in another lane, its base and length fetched from it
+			// (__shfl, which lowers to ds_bpermute); a chunk is loaded only
+			// if it starts inside the frame (len 0 past the batch's end: no
+			// load).  The 16-byte loads rely on the ABI's frame alignment
+			// (include/xdpfilter_gpu.h: frame starts are 16-byte aligned),
+			// as the general kernel's window loads do.
+			const bool in = (uint32_t)lane < rem;
+			const uint64_t off = in ? (((uint64_t)(dsc.y & 0xffffu) << 32) | dsc.x) + (dsc.y >> 16) : 0;
+			const uint32_t dlen = in ? dsc.z : 0;
+			const uint64_t um = (uint64_t)(uintptr_t)a.data;
+#pragma unroll
+			for (int it = 0; it < CPP; it++) {
+				const uint32_t c = it * 64 + lane, pk = c / CPP, sub = c % CPP;
+				const uint32_t olo = __shfl((uint32_t)off, (int)pk);
+				const uint32_t ohi = __shfl((uint32_t)(off >> 32), (int)pk);
+				const uint32_t ln = __shfl(dlen, (int)pk);
+				pre[it] = u32x4{ 0, 0, 0, 0 };
+				if (sub * 16 < ln)
+					pre[it] = __builtin_nontemporal_load(reinterpret_cast<gu32x4 *>(
+						um + (((uint64_t)ohi << 32) | olo) + sub * 16));
+			}
+			plen = dlen;
+			return;
+		}
 		if constexpr (DENSE) {
 			const u32x4 *src = reinterpret_cast<const u32x4 *>(a.data + (uint64_t)base * W) + lane;
 #pragma unroll
@@ -581,7 +643,19 @@ __global__ __launch_bounds__(PIPE_THREADS(W), (W) <= 64 ? 4 : 2) void xfg_pipeli
 	uint32_t r_act = A_NONE, r_tag = CT_NONE, r_len = 0;
 	bool r_sel = false, r_more = false;
 
-	if (first < nt)
+	if constexpr (DESC) {
+		// (the prologue's one dependent hop: the first tile's records, then
+		// its windows; the second tile's records are in flight into the loop.
+		// A wave with no tile loads nothing, one with a single tile no
+		// second record)
+		if (first < nt) {
+			load_desc(first);
+			__builtin_amdgcn_s_waitcnt(0x0F70);
+			issue(first);
+			if (first + step < nt)
+				load_desc(first + step);
+		}
+	} else if (first < nt)
 		issue(first);
 	for (uint32_t k = 0;; k++) {
 		const uint32_t tP = first + k * step;
@@ -709,6 +783,10 @@ __global__ __launch_bounds__(PIPE_THREADS(W), (W) <= 64 ? 4 : 2) void xfg_pipeli
 		// tile k+1's windows: in flight until the next iteration's staging
 		if (tP + step < nt)
 			issue(tP + step);
+		// ---- D: tile k+2's records (after issue() has consumed tile k+1's)
+		if constexpr (DESC)
+			if (tP + 2 * step < nt)
+				load_desc(tP + 2 * step);
 
 		// ---- P: parse tile k, plan its lookups, issue the Bloom words
 		if (vP) {
@@ -761,7 +839,8 @@ __global__ __launch_bounds__(PIPE_THREADS(W), (W) <= 64 ? 4 : 2) void xfg_pipeli
 		uint32_t act = A_NONE, tag = CT_NONE, len = 0;
 		if (d0 + lane < ndef) {
 			const uint32_t gi = gld32(dlist + d0 + lane);
-			len = min(load_len(a, gi), a.stride);
+			// (a slot bounds its frame; a descriptor's length is the frame's)
+			len = DESC ? load_len(a, gi) : min(load_len(a, gi), a.stride);
 			act = classify_one<FEAT>(a, s_ports, gi, len, tag);
 			__builtin_nontemporal_store((uint8_t)act, a.verdicts + gi);
 		}

@@ -61,7 +61,7 @@ EXPORTS = [
     "xfg_host_alloc_pinned", "xfg_host_free_pinned", "xfg_classify_timed", "xfg_stream_read_timed",
     "xfg_comm_unique_id", "xfg_comm_init", "xfg_comm_allreduce", "xfg_map_update_batch_percpu",
     "xfg_classify_descs", "xfg_compact", "xfg_classify_xsk_host", "xfg_host_register",
-    "xfg_host_unregister", "xfg_last_path", "xfg_host_threads",
+    "xfg_host_unregister", "xfg_last_path", "xfg_host_threads", "xfg_classify_descs_timed",
 ]
 # include/xdpfilter_io.h
 IO_EXPORTS = [
@@ -77,7 +77,8 @@ class OpenOpts(C.Structure):
                 ("devices", C.POINTER(C.c_int)), ("ndev", C.c_int),
                 ("ipv4_capacity", C.c_uint32), ("ipv6_capacity", C.c_uint32),
                 ("eth_capacity", C.c_uint32), ("hash_seed", C.c_uint32),
-                ("qt_min_keys", C.c_uint32), ("window", C.c_uint32)]
+                ("qt_min_keys", C.c_uint32), ("window", C.c_uint32), ("reserved0", C.c_uint32),
+                ("descs_min_packets", C.c_uint32)]
 
 
 class Batch(C.Structure):
@@ -148,6 +149,8 @@ def _load():
         "xfg_compact": (C.c_int, [vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp, vp]),
         "xfg_classify_timed": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.c_int,
                                          C.POINTER(C.c_double)]),
+        "xfg_classify_descs_timed": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp, C.c_int,
+                                               C.POINTER(C.c_double)]),
         "xfg_stream_read_timed": (C.c_int, [vp, C.c_int, vp, C.c_uint64, C.c_int,
                                             C.POINTER(C.c_double)]),
         "xfg_stats_read": (C.c_int, [vp, C.POINTER(StatsRecord)]),
@@ -273,7 +276,7 @@ class Filter:
 
     def __init__(self, features=FEAT_ALL | FEAT_DENY, devices=None, ndev=None,
                  ipv4_capacity=0, ipv6_capacity=0, eth_capacity=0, hash_seed=0, qt_min_keys=0,
-                 window=0):
+                 window=0, descs_min_packets=0):
         opts = OpenOpts()
         opts.sz = C.sizeof(OpenOpts)
         opts.features = features
@@ -290,6 +293,7 @@ class Filter:
         opts.hash_seed = hash_seed
         opts.qt_min_keys = qt_min_keys
         opts.window = window
+        opts.descs_min_packets = descs_min_packets
         ctx = C.c_void_p()
         _check(lib.xfg_open(C.byref(ctx), C.byref(opts)), "xfg_open")
         self.ctx = ctx
@@ -420,6 +424,16 @@ class Filter:
         b = DescBatch(umem_ptr, descs_ptr, first, mask, count)
         _check(lib.xfg_classify_descs(self.ctx, dev, C.byref(b), verdicts_ptr, stream),
                "classify_descs")
+
+    def classify_descs_timed(self, umem_ptr, descs_ptr, count, verdicts_ptr, iters, first=0,
+                             mask=0xffffffff, dev=0):
+        """@iters launches of a descriptor batch; the average ms of one
+        (xfg_classify_descs_timed)."""
+        b = DescBatch(umem_ptr, descs_ptr, first, mask, count)
+        ms = C.c_double()
+        _check(lib.xfg_classify_descs_timed(self.ctx, dev, C.byref(b), verdicts_ptr, iters,
+                                            C.byref(ms)), "classify_descs_timed")
+        return ms.value
 
     def host_register(self, arr: np.ndarray):
         """Pin and map a long-lived host array: the kernels read batches in it
