@@ -290,6 +290,73 @@ int xfg_classify_xsk_host(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *ba
 int xfg_compact(xfg_ctx *ctx, int dev, const uint8_t *verdicts, uint64_t n, uint32_t action,
 		uint32_t *idx, uint64_t *count, void *stream);
 
+/*
+ * AF_XDP egress: the TX and fill ring records of a classified RX batch, built
+ * on the device -- what an AF_XDP consumer does with a received batch, per
+ * packet by its verdict.  Packet i is RX record rx_descs[(rx_first + i) &
+ * rx_mask], a struct xdp_desc as for xfg_classify_descs, and @verdicts holds
+ * its verdict byte (device memory, count bytes).
+ *
+ * The k-th packet in packet order whose verdict is XFG_XDP_PASS becomes TX
+ * record tx_descs[(tx_first + k) & tx_mask]: addr as received (the
+ * unaligned-chunk form, offset in bits 48..63, stays), len as received,
+ * options 0 -- l2fwd()'s tx_desc->addr = orig; tx_desc->len = len
+ * (lib/util/xdpsock.c:1466-1550).  The j-th packet with any other verdict
+ * byte hands its chunk back: fill_addrs[(fill_first + j) & fill_mask] = addr &
+ * ((1 << 48) - 1), rx_drop()'s *xsk_ring_prod__fill_addr(fq, idx_fq++) =
+ * xsk_umem__extract_addr(addr) (lib/util/xdpsock.c:1199-1258,
+ * headers/xdp/xsk.h:173-176).  counts[0] = TX records, counts[1] = fill
+ * addresses (device memory, two u64): the caller submits that many entries
+ * of each ring; entries past them are not written.  Peek, reserve, submit
+ * and release stay with the caller.
+ *
+ * tx_descs == NULL: every chunk goes to the fill ring (rx_drop); @verdicts is
+ * not read and may be NULL.  fill_addrs == NULL: only the TX ring is written;
+ * counts[1] still counts the other frames.  Both NULL: -EINVAL.
+ *
+ * XFG_EGRESS_SWAP_MACS: bytes 0..5 and 6..11 of every PASS frame change
+ * places in the UMEM (swap_mac_addresses(), lib/util/xdpsock.c:646-654), by
+ * one 16-byte load and store of the frame's first 16 bytes: frame starts are
+ * 16-byte aligned as for xfg_classify_descs, and a PASS frame is at least 14
+ * bytes long (every program aborts a shorter one).  With this flag the
+ * descriptors of one batch must name distinct frames (two records of one
+ * frame would race on its bytes).
+ *
+ * A mask is ring entries - 1 (a power of two), or 0xffffffff for a plain
+ * array; an index first + i wraps modulo 2^32 before the mask.  The caller
+ * reserves count entries of each output ring (as xsk_ring_prod__reserve(..,
+ * rcvd, ..) does), so a ring of fewer entries is refused.  The TX and fill
+ * rings must not overlap the RX ring or each other (not checked).
+ *
+ * -EINVAL: sz below the structure's size, a mask that is not 2^k - 1, an
+ * output ring of fewer than count entries, a pointer that is not 8-byte
+ * aligned, count >= 2^32, counts == NULL, unknown flag bits, SWAP_MACS
+ * without umem, no RX ring or no verdicts where they are read.  -ENODEV on a
+ * host-only context.  count == 0 writes two zero counts and nothing else.
+ *
+ * Stream-ordered on @stream (NULL: the library's stream of the device), as
+ * xfg_compact is: after xfg_classify_descs on the same stream it needs no
+ * host synchronisation.  Single-buffer descriptors only.
+ */
+#define XFG_EGRESS_SWAP_MACS (1u << 0)
+
+struct xfg_egress {
+	size_t sz;              /* sizeof(struct xfg_egress), for extension */
+	void *umem;             /* written only with SWAP_MACS; else may be NULL */
+	const void *rx_descs;
+	uint32_t rx_first, rx_mask;
+	void *tx_descs;         /* NULL: all frames to the fill ring */
+	uint32_t tx_first, tx_mask;
+	uint64_t *fill_addrs;   /* NULL: TX ring only */
+	uint32_t fill_first, fill_mask;
+	uint64_t count;         /* < 2^32 */
+	uint64_t *counts;       /* device memory, 2 x u64 */
+	uint32_t flags;
+};
+
+int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e,
+		    const uint8_t *verdicts, void *stream);
+
 /* Per-action stats summed over devices (the userspace per-CPU sum of
  * lib/util/stats.c:140-172), or for one device. */
 int xfg_stats_read(xfg_ctx *ctx, struct xfg_stats_record out[XFG_ACTION_MAX]);

@@ -22,6 +22,11 @@
       descriptor mode) and, strided, on the generic pipelined kernel
       (XFG_KERNEL=generic) and the quotient-index kernel.  2^22 packets by
       default: an 8 GiB UMEM (the workload's 2^24 would need 32 GiB)
+  c3f  c3d's batch classified, then its egress (xfg_ring_egress): TX records of
+      the PASS frames and fill addresses of the others, with and without the
+      MAC swap, beside xfg_compact on the same verdicts -- each timed over
+      --iters launches between events on a caller stream, with the bytes
+      moved and their share of this device's streaming-read rate
 
   c1  xdpfilt_alw_eth, the 8 MAC rules 02:00:00:00:00:0{1..8} (4 dst, 4
       src), 64 B Ethernet/IPv4/UDP frames, 25% carrying a ruled MAC (SURVEY.md
@@ -108,7 +113,10 @@ def run_c1(args):
 C3D_CHUNK, C3D_HEADROOM = 2048, 256
 
 
-def run_c3d(args):
+def c3d_workload(args, tag):
+    """C3's frames in a device UMEM behind an RX ring that wraps, the rules
+    loaded (c3d, c3f).  Returns a namespace of what the legs use."""
+    import types
     import numpy as np
     import xftools as X
     import xfgpu as G
@@ -150,7 +158,17 @@ def run_c3d(args):
     d_descs, d_verd = f.alloc(descs.nbytes), f.alloc(n)
     d_descs.upload(descs)
     setup_s = time.time() - t0
-    print(f"[c3d] set up {setup_s:.1f}s", file=sys.stderr, flush=True)
+    print(f"[{tag}] set up {setup_s:.1f}s", file=sys.stderr, flush=True)
+    return types.SimpleNamespace(f=f, n=n, n4=n4, nports=nports, stride=stride, data=data, lens=lens,
+                                 d_umem=d_umem, d_descs=d_descs, d_verd=d_verd, entries=entries,
+                                 first=first, setup_s=setup_s)
+
+
+def run_c3d(args):
+    w = c3d_workload(args, "c3d")
+    f, n, n4, nports, stride, data, lens = w.f, w.n, w.n4, w.nports, w.stride, w.data, w.lens
+    d_umem, d_descs, d_verd, entries, first, setup_s = (w.d_umem, w.d_descs, w.d_verd, w.entries,
+                                                        w.first, w.setup_s)
 
     def descs_ms():
         a = (d_umem.ptr, d_descs.ptr, n, d_verd.ptr)
@@ -193,6 +211,72 @@ def run_c3d(args):
     print(json.dumps(line), flush=True)
 
 
+def run_c3f(args):
+    """c3d's batch classified, then its egress (xfg_ring_egress): TX records
+    of the PASS frames, fill addresses of the rest.  Each leg is args.iters
+    launches between two events on a caller stream, args.runs times."""
+    import numpy as np
+    import torch
+    import xfgpu as G
+    w = c3d_workload(args, "c3f")
+    f, n, entries, first = w.f, w.n, w.entries, w.first
+    f.classify_descs(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, first=first, mask=entries - 1)
+    f.sync()
+    npass = int(np.count_nonzero(w.d_verd.download(np.zeros(n, np.uint8)) == 2))
+    # TX and fill rings of the batch's size, each wrapping inside it
+    d_tx, d_fill, d_idx, d_c = f.alloc(16 * n), f.alloc(8 * n), f.alloc(4 * n), f.alloc(16)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def egress(flags):
+        f.ring_egress(w.d_descs.ptr, n, w.d_verd.ptr, d_c.ptr, tx_ptr=d_tx.ptr, fill_ptr=d_fill.ptr,
+                      rx_first=first, rx_mask=entries - 1, tx_first=n - 777, tx_mask=n - 1,
+                      fill_first=n - 555, fill_mask=n - 1, umem_ptr=w.d_umem.ptr, flags=flags,
+                      stream=sp)
+
+    legs = {"compact": lambda: f.compact(w.d_verd.ptr, n, 2, d_idx.ptr, d_c.ptr, stream=sp),
+            "egress": lambda: egress(0),
+            "egress_swap_macs": lambda: egress(G.EGRESS_SWAP_MACS)}
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            call()
+        e0.record(stream)
+        for _ in range(args.iters):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    runs = max(1, args.runs)
+    ms = {k: [] for k in legs}
+    for _ in range(runs):      # the legs interleaved
+        for k, call in legs.items():
+            ms[k].append(timed(call))
+    counts = d_c.download(np.zeros(2, np.uint64)).tolist()
+    assert counts == [npass, n - npass], counts
+    # this device's own streaming-read rate, over the UMEM's first GiB
+    probe = min(n * C3D_CHUNK, 1 << 30)
+    f.stream_read_timed(w.d_umem.ptr, probe, 2)
+    read_gbs = probe / (f.stream_read_timed(w.d_umem.ptr, probe, args.iters) * 1e-3) / 1e9
+    # bytes the algorithm moves: a record and a verdict byte read a packet,
+    # a TX record or a fill address written; the swap reads and writes 16 B
+    # of every PASS frame
+    moved = {"compact": n + 4 * npass, "egress": 17 * n + 16 * npass + 8 * (n - npass)}
+    moved["egress_swap_macs"] = moved["egress"] + 32 * npass
+    line = {"config": "c3f", "program": f.prog_name, "packets": n, "pass_frames": npass,
+            "ring_entries": entries, "iters": args.iters, "stream_read_GBps": round(read_gbs, 1),
+            "setup_s": round(w.setup_s, 1)}
+    for k in legs:
+        best = min(ms[k])
+        gbs = moved[k] / (best * 1e-3) / 1e9
+        line[k] = {"ms": [round(m, 4) for m in ms[k]], "bytes": moved[k], "GBps": round(gbs, 1),
+                   "frac_of_stream_read": round(gbs / read_gbs, 3)}
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
 def run(name, args):
     import numpy as np
     import xftools as X
@@ -201,6 +285,8 @@ def run(name, args):
         return run_c1(args)
     if name == "c3d":
         return run_c3d(args)
+    if name == "c3f":
+        return run_c3f(args)
     kind = {"c2": 2, "c3": 3, "c4": 4, "c5": 5, "c3sd": 3, "c3e": 3}[name]
     n = 1 << (args.log2_packets or {"c2": 24, "c3": 24, "c4": 23, "c5": 23, "c3sd": 24, "c3e": 24}[name])
     stride = 64 if kind in (2, 3) else 1536

@@ -40,6 +40,7 @@ int xfg_launch_compact(const uint8_t *verdicts, uint64_t n, uint32_t action, uin
 		       unsigned long long *count, unsigned long long *status, uint32_t *ticket,
 		       unsigned grid, void *stream);
 uint64_t xfg_compact_tiles(uint64_t n);
+int xfg_launch_egress(const struct xfg_egress_kargs *a, unsigned grid, void *stream);
 int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 		       unsigned long long *hits, uint32_t n, void *stream);
 
@@ -148,7 +149,7 @@ struct xfg_dev {
 	uint32_t log_cw, log_first;
 	uint32_t *rec;                  /* split classify: parse-pass records */
 	uint64_t rec_bytes;
-	unsigned long long *cstatus;    /* verdict compaction: tile status words */
+	unsigned long long *cstatus;    /* verdict compaction, egress: tile status words */
 	uint64_t cstatus_cap;
 	uint32_t *cticket;
 	hipEvent_t ev_user, ev_done;    /* ordering against a caller's stream */
@@ -2271,6 +2272,25 @@ fail:
 	return err;
 }
 
+/* Room for @words status words in the device's tile status buffer (d->lock
+ * held, the device current): shared by xfg_compact and xfg_ring_egress, whose
+ * launches run one after the other on the device's stream and each zero the
+ * words they use first. */
+static int cstatus_room(struct xfg_dev *d, uint64_t words)
+{
+	int err = 0;
+	if (words <= d->cstatus_cap)
+		return 0;
+	HIPCHK(hipStreamSynchronize(d->stream));   /* the old buffer may be in use */
+	hipFree(d->cstatus);
+	d->cstatus = NULL;
+	d->cstatus_cap = 0;
+	HIPCHK(hipMalloc((void **)&d->cstatus, words * 8));
+	d->cstatus_cap = words;
+fail:
+	return err;
+}
+
 /* Verdict compaction (include/xdpfilter_gpu.h).  The kernel uses per-device
  * scratch (tile status words, ticket), so it runs on the device's own stream,
  * ordered after and before the caller's stream: two compactions never
@@ -2291,14 +2311,8 @@ int xfg_compact(xfg_ctx *ctx, int dev, const uint8_t *verdicts, uint64_t n, uint
 	HIPCHK(hipSetDevice(d->ordinal));
 	if (!d->cticket)
 		HIPCHK(hipMalloc((void **)&d->cticket, 4));
-	if (tiles > d->cstatus_cap) {
-		HIPCHK(hipStreamSynchronize(d->stream));   /* the old buffer may be in use */
-		hipFree(d->cstatus);
-		d->cstatus = NULL;
-		d->cstatus_cap = 0;
-		HIPCHK(hipMalloc((void **)&d->cstatus, tiles * 8));
-		d->cstatus_cap = tiles;
-	}
+	if ((err = cstatus_room(d, tiles)))
+		goto fail;
 	hipStream_t user = (hipStream_t)stream;
 	if (user && user != d->stream) {
 		HIPCHK(hipEventRecord(d->ev_user, user));
@@ -2306,6 +2320,75 @@ int xfg_compact(xfg_ctx *ctx, int dev, const uint8_t *verdicts, uint64_t n, uint
 	}
 	err = xfg_launch_compact(verdicts, n, action, idx, (unsigned long long *)count,
 				 d->cstatus, d->cticket, (unsigned)d->ncu * 4, d->stream);
+	if (!err && user && user != d->stream) {
+		HIPCHK(hipEventRecord(d->ev_done, d->stream));
+		HIPCHK(hipStreamWaitEvent(user, d->ev_done, 0));
+	}
+fail:
+	pthread_mutex_unlock(&d->lock);
+	return err;
+}
+
+/* a ring mask: 2^k - 1 (0xffffffff: a plain array) */
+static int mask_ok(uint32_t mask)
+{
+	return !(mask & (mask + 1u));
+}
+
+/* AF_XDP egress (include/xdpfilter_gpu.h).  Like xfg_compact it runs on the
+ * device's own stream between the two events, over the same status buffer:
+ * a compaction and an egress, or two of either, never overlap on a device. */
+int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uint8_t *verdicts,
+		    void *stream)
+{
+	int err = 0;
+	if (!ctx || !e || e->sz < sizeof(*e) || !e->counts || ((uintptr_t)e->counts & 7) ||
+	    (e->flags & ~XFG_EGRESS_SWAP_MACS) || e->count > 0xffffffffull ||
+	    (!e->tx_descs && !e->fill_addrs))
+		return -EINVAL;
+	if (!mask_ok(e->rx_mask) || !mask_ok(e->tx_mask) || !mask_ok(e->fill_mask))
+		return -EINVAL;
+	if (((uintptr_t)e->rx_descs & 7) || ((uintptr_t)e->tx_descs & 7) ||
+	    ((uintptr_t)e->fill_addrs & 7) || ((uintptr_t)e->umem & 7))
+		return -EINVAL;
+	if ((e->tx_descs && (uint64_t)e->tx_mask + 1 < e->count) ||
+	    (e->fill_addrs && (uint64_t)e->fill_mask + 1 < e->count))
+		return -EINVAL;
+	if ((e->flags & XFG_EGRESS_SWAP_MACS) && !e->umem)
+		return -EINVAL;
+	if (e->count && (!e->rx_descs || (e->tx_descs && !verdicts)))
+		return -EINVAL;
+	if (!ctx->ndev)
+		return -ENODEV;
+	if (dev < 0 || dev >= ctx->ndev)
+		return -EINVAL;
+	struct xfg_dev *d = &ctx->dev[dev];
+	hipStream_t user = (hipStream_t)stream;
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!e->count) {   /* no scratch: on the caller's stream itself */
+		HIPCHK(hipMemsetAsync(e->counts, 0, 16, user ? user : d->stream));
+		goto fail;
+	}
+	if ((err = cstatus_room(d, XFG_EGRESS_STATE_WORDS(e->count))))
+		goto fail;
+	struct xfg_egress_kargs a = {
+		.umem = (e->flags & XFG_EGRESS_SWAP_MACS) ? e->umem : NULL,
+		.rx = e->rx_descs, .tx = e->tx_descs, .fill = e->fill_addrs,
+		.verdicts = verdicts, .counts = (unsigned long long *)e->counts,
+		.state = d->cstatus,
+		.rx_first = e->rx_first, .rx_mask = e->rx_mask,
+		.tx_first = e->tx_first, .tx_mask = e->tx_mask,
+		.fill_first = e->fill_first, .fill_mask = e->fill_mask,
+		.n = (uint32_t)e->count,
+		.swap_macs = !!(e->flags & XFG_EGRESS_SWAP_MACS),
+	};
+	if (user && user != d->stream) {
+		HIPCHK(hipEventRecord(d->ev_user, user));
+		HIPCHK(hipStreamWaitEvent(d->stream, d->ev_user, 0));
+	}
+	/* (four workgroups a CU: all of them resident) */
+	err = xfg_launch_egress(&a, (unsigned)d->ncu * 4, d->stream);
 	if (!err && user && user != d->stream) {
 		HIPCHK(hipEventRecord(d->ev_done, d->stream));
 		HIPCHK(hipStreamWaitEvent(user, d->ev_done, 0));

@@ -2220,4 +2220,8 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 	return (n + CT_TILE - 1) / CT_TILE;
 }
 
+// AF_XDP egress (TX and fill ring records from verdicts): the same tile
+// scheme and status words over 16-byte records
+#include "xfg_egress.hip"
+
 #endif   // XFG_PART_COMMON

@@ -290,6 +290,30 @@ struct xfg_kargs {
 	uint32_t cw_s0;
 };
 
+/* Arguments of the egress kernel (xfg_egress.hip, xfg_ring_egress()): the RX
+ * records, the two output rings (either may be NULL) and the launch's state
+ * words in device memory -- word 0 the tile ticket, word 1 padding, from
+ * word 2 one status word a tile (XFG_EGRESS_STATE_WORDS() of them, zeroed by
+ * the launch function). */
+struct xfg_egress_kargs {
+	uint8_t *umem;                  /* written only with swap_macs */
+	const void *rx;
+	void *tx;
+	uint64_t *fill;
+	const uint8_t *verdicts;        /* read only with tx */
+	unsigned long long *counts;     /* {TX records, fill addresses} */
+	unsigned long long *state;
+	uint32_t rx_first, rx_mask;
+	uint32_t tx_first, tx_mask;
+	uint32_t fill_first, fill_mask;
+	uint32_t n;                     /* packets, >= 1 */
+	uint32_t swap_macs;
+};
+#define XFG_EGRESS_TILE 2048u   /* packets a tile: 256 lanes x 8 passes */
+#define XFG_EGRESS_TILES(n) (((uint64_t)(n) + XFG_EGRESS_TILE - 1) / XFG_EGRESS_TILE)
+/* (an even count: the launch's one memset is then a multiple of 16 bytes) */
+#define XFG_EGRESS_STATE_WORDS(n) ((XFG_EGRESS_TILES(n) + 3) & ~1ull)
+
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 #define XFG_HD __host__ __device__ __forceinline__

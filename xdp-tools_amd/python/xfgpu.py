@@ -62,7 +62,9 @@ EXPORTS = [
     "xfg_comm_unique_id", "xfg_comm_init", "xfg_comm_allreduce", "xfg_map_update_batch_percpu",
     "xfg_classify_descs", "xfg_compact", "xfg_classify_xsk_host", "xfg_host_register",
     "xfg_host_unregister", "xfg_last_path", "xfg_host_threads", "xfg_classify_descs_timed",
+    "xfg_ring_egress",
 ]
+EGRESS_SWAP_MACS = 1
 # include/xdpfilter_io.h
 IO_EXPORTS = [
     "xfg_pcap_read", "xfg_host_batch_free", "xfg_pcapng_write_verdicts", "xfg_store_map_name",
@@ -93,6 +95,15 @@ class StatsRecord(C.Structure):
 class DescBatch(C.Structure):
     _fields_ = [("umem", C.c_void_p), ("descs", C.c_void_p), ("first", C.c_uint32),
                 ("mask", C.c_uint32), ("count", C.c_uint64)]
+
+
+class Egress(C.Structure):
+    """struct xfg_egress (xfg_ring_egress)."""
+    _fields_ = [("sz", C.c_size_t), ("umem", C.c_void_p),
+                ("rx_descs", C.c_void_p), ("rx_first", C.c_uint32), ("rx_mask", C.c_uint32),
+                ("tx_descs", C.c_void_p), ("tx_first", C.c_uint32), ("tx_mask", C.c_uint32),
+                ("fill_addrs", C.c_void_p), ("fill_first", C.c_uint32), ("fill_mask", C.c_uint32),
+                ("count", C.c_uint64), ("counts", C.c_void_p), ("flags", C.c_uint32)]
 
 
 class HostBatch(C.Structure):
@@ -147,6 +158,7 @@ def _load():
         "xfg_host_unregister": (C.c_int, [vp, vp]),
         "xfg_host_threads": (C.c_int, []),
         "xfg_compact": (C.c_int, [vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp, vp]),
+        "xfg_ring_egress": (C.c_int, [vp, C.c_int, C.POINTER(Egress), vp, vp]),
         "xfg_classify_timed": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.c_int,
                                          C.POINTER(C.c_double)]),
         "xfg_classify_descs_timed": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp, C.c_int,
@@ -458,6 +470,18 @@ class Filter:
     def compact(self, verdicts_ptr, n, action, idx_ptr, count_ptr, dev=0, stream=None):
         _check(lib.xfg_compact(self.ctx, dev, verdicts_ptr, n, action, idx_ptr, count_ptr, stream),
                "compact")
+
+    def ring_egress(self, rx_ptr, count, verdicts_ptr, counts_ptr, tx_ptr=None, fill_ptr=None,
+                    rx_first=0, rx_mask=0xffffffff, tx_first=0, tx_mask=0xffffffff,
+                    fill_first=0, fill_mask=0xffffffff, umem_ptr=None, flags=0, dev=0,
+                    stream=None):
+        """TX records of the PASS frames and fill addresses of the others from
+        an RX descriptor batch and its verdicts (xfg_ring_egress); device
+        pointers, counts_ptr: two u64 {TX records, fill addresses}."""
+        e = Egress(C.sizeof(Egress), umem_ptr, rx_ptr, rx_first, rx_mask, tx_ptr, tx_first,
+                   tx_mask, fill_ptr, fill_first, fill_mask, count, counts_ptr, flags)
+        _check(lib.xfg_ring_egress(self.ctx, dev, C.byref(e), verdicts_ptr, stream),
+               "ring_egress")
 
     def classify_timed(self, data_ptr, lens_ptr, count, stride, verdicts_ptr, iters,
                        offsets_ptr=None, lens_u16=False, dev=0):
