@@ -357,6 +357,65 @@ struct xfg_egress {
 int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e,
 		    const uint8_t *verdicts, void *stream);
 
+/*
+ * Capture by verdict: the frames of a device-resident batch that a program
+ * dropped (or passed, or aborted), as finished pcapng Enhanced Packet Blocks
+ * in one contiguous device buffer -- what xdpdump records at a program's exit
+ * with the verdict in each record, cut to --snapshot-length
+ * (xdp-dump/xdpdump.c:51,100,132,502; lib/util/xpcapng.c:392-479).  Only that
+ * buffer crosses PCIe; xfg_pcapng_append() (xdpfilter_io.h) adds it to a file
+ * begun with xfg_pcapng_begin() as it is.
+ *
+ * Frame i is selected if its verdict byte v = verdicts[i] is below 32 and bit
+ * v of action_mask is set.  Its block is the one xfg_pcapng_write_captured()
+ * writes, byte for byte (the layout is stated there): cap = snaplen ?
+ * min(len, snaplen) : len frame bytes, L = 52 + ((cap + 3) & ~3) bytes in
+ * all, len the batch's length of the frame (data_end - data: as for the
+ * classify calls a fixed-stride slot bounds it), the timestamp ts_ns[i] or
+ * ts0, the option epb_verdict = {2 (eBPF XDP), u64 v}.
+ *
+ * The blocks lie in packet order from out + 0 without gaps: frame k's block
+ * starts at the sum of the lengths of the selected frames before it.  A block
+ * is written only if it ends at or before out_bytes; starts only grow, so the
+ * written blocks are a prefix of the selected frames (a later, smaller frame
+ * is not slipped in).  counts[0] = blocks written, counts[1] = their bytes,
+ * counts[2] = selected frames not written.  Bytes of out at or past counts[1]
+ * are not written.
+ *
+ * Every source form of the two batch structures is taken, under the alignment
+ * and read-past rules stated with them (frame starts 16-byte aligned, readable
+ * to the next 16-byte boundary past the end).  A block is shorter than 2^25
+ * bytes (64 consecutive ones are addressed with 32 bits).  count < 2^32; byte
+ * positions in out are 64-bit.
+ *
+ * -EINVAL: sz below the structure's size, counts == NULL, out == NULL with
+ * out_bytes != 0, out not 16-byte or counts / ts_ns not 8-byte aligned,
+ * verdicts == NULL with count != 0, a bad batch (as the classify calls
+ * refuse it: a mask that is not 2^k - 1, a stride that is no multiple of 16,
+ * ...), count >= 2^32.  -ENODEV on a host-only context.  count == 0 or
+ * action_mask == 0 writes three zero counts and nothing else.
+ *
+ * Stream-ordered on @stream (NULL: the library's stream of the device), as
+ * xfg_compact and xfg_ring_egress are: after a classify call on the same
+ * stream it needs no host synchronisation.  The call changes no map, counter
+ * or statistic.  Single-buffer descriptors only.
+ */
+struct xfg_capture {
+	size_t sz;              /* sizeof(struct xfg_capture), for extension */
+	uint32_t action_mask;   /* bit a: capture frames whose verdict byte is a (< 32) */
+	uint32_t snaplen;       /* 0: whole frames */
+	const uint64_t *ts_ns;  /* device, one per packet; NULL: every frame gets ts0 */
+	uint64_t ts0;
+	void *out;              /* device, 16-byte aligned */
+	uint64_t out_bytes;
+	uint64_t *counts;       /* device, 3 x u64 */
+};
+
+int xfg_capture(xfg_ctx *ctx, int dev, const struct xfg_batch *batch, const uint8_t *verdicts,
+		const struct xfg_capture *cap, void *stream);
+int xfg_capture_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
+		      const uint8_t *verdicts, const struct xfg_capture *cap, void *stream);
+
 /* Per-action stats summed over devices (the userspace per-CPU sum of
  * lib/util/stats.c:140-172), or for one device. */
 int xfg_stats_read(xfg_ctx *ctx, struct xfg_stats_record out[XFG_ACTION_MAX]);

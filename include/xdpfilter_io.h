@@ -63,6 +63,32 @@ void xfg_host_batch_free(struct xfg_host_batch *b);
 int xfg_pcapng_write_verdicts(const char *path, const char *ifname,
 			      const struct xfg_host_batch *b, const uint8_t *verdicts);
 
+/* Capture by verdict, what xdpdump answers at a program's exit
+ * (xdp-dump/xdpdump.c:51,100,132,502): the same section and interface blocks
+ * (the IDB's snaplen field = @snaplen, 0: none), then in packet order one EPB
+ * for each frame i with verdicts[i] < 32 && (action_mask >> verdicts[i]) & 1,
+ * cut to @snaplen bytes (0: whole).  The block, little endian:
+ *
+ *   cap = snaplen ? min(lens[i], snaplen) : lens[i];  cap4 = (cap + 3) & ~3
+ *   u32 {6, L, 0, ts >> 32, (u32)ts, cap, len}        L = 52 + cap4
+ *   cap frame bytes, cap4 - cap zero bytes
+ *   u16 {7, 9}, u8 2, u64 verdict, 3 zero bytes       epb_verdict, eBPF XDP
+ *   u32 {0, L}
+ *
+ * len is orig_lens[i], or lens[i] without that array; ts is ts_ns[i] or 0.
+ * This function is the CPU statement of the format: xfg_capture() in
+ * xdpfilter_gpu.h lays down the same bytes on the device. */
+int xfg_pcapng_write_captured(const char *path, const char *ifname,
+			      const struct xfg_host_batch *b, const uint8_t *verdicts,
+			      uint32_t action_mask, uint32_t snaplen);
+
+/* A capture file written in pieces: begin creates or truncates @path and
+ * writes the section and interface blocks of xfg_pcapng_write_captured();
+ * append adds @bytes of finished blocks (xfg_capture()'s output as it is).
+ * -EINVAL if @bytes is not a multiple of 4. */
+int xfg_pcapng_begin(const char *path, const char *ifname, uint32_t snaplen);
+int xfg_pcapng_append(const char *path, const void *blocks, uint64_t bytes);
+
 /* ---- f2: rule store -------------------------------------------------------- */
 /* Map file names, as pinned by the reference (xdp-filter/common_kern_user.h:
  * 21-26, headers/xdp/xdp_stats_kern_user.h:8). */

@@ -27,8 +27,12 @@
       MAC swap, beside xfg_compact on the same verdicts -- each timed over
       --iters launches between events on a caller stream, with the bytes
       moved and their share of this device's streaming-read rate
+  c3c  c3d's batch classified, then its DROP frames captured as pcapng blocks
+      (xfg_capture_descs, snaplen 0), beside xfg_compact; the same ring with
+      1514-byte frames at snaplen 96, one in ten selected; one tile of
+      packets for the fixed cost of a call -- timed as c3f's legs are
 
-  c1  xdpfilt_alw_eth, the 8 MAC rules 02:00:00:00:00:0{1..8} (4 dst, 4
+  c1 xdpfilt_alw_eth, the 8 MAC rules 02:00:00:00:00:0{1..8} (4 dst, 4
       src), 64 B Ethernet/IPv4/UDP frames, 25% carrying a ruled MAC (SURVEY.md
       §8d: BASELINE.json configs[0], the reference's in-kernel CPU case): the
       GPU path, and the CPU restatement timed on the same batch on 1 thread
@@ -277,12 +281,103 @@ def run_c3f(args):
     print(json.dumps(line), flush=True)
 
 
+def run_c3c(args):
+    """c3d's batch classified, then its DROP frames captured whole as pcapng
+    blocks (xfg_capture_descs), beside xfg_compact on the same verdicts; then
+    the same ring with every frame 1514 bytes long, one frame in ten selected,
+    cut to 96 bytes; and a one-tile batch for the fixed cost of a call.  Each
+    leg is args.iters launches between two events on a caller stream."""
+    import numpy as np
+    import torch
+    import xfgpu as G
+    w = c3d_workload(args, "c3c")
+    f, n, entries, first = w.f, w.n, w.entries, w.first
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    f.classify_descs(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, first=first, mask=entries - 1)
+    f.sync()
+    verd = w.d_verd.download(np.zeros(n, np.uint8))
+    ndrop = int(np.count_nonzero(verd == 1))
+    # second setting: the same chunks, 1514-byte frames, 10 % DROP
+    rng = np.random.default_rng(13)
+    verd10 = np.where(rng.random(n) < 0.1, 1, 2).astype(np.uint8)
+    n10 = int(np.count_nonzero(verd10 == 1))
+    descs = w.d_descs.download(np.zeros((entries, 2), np.uint64))
+    descs[:, 1] = 1514
+    d_descs10, d_verd10 = f.alloc(descs.nbytes), f.alloc(n)
+    d_descs10.upload(descs)
+    d_verd10.upload(verd10)
+    blk = 52 + ((w.lens.astype(np.int64) + 3) & ~3)
+    total = int(blk[verd == 1].sum())
+    total10 = n10 * (52 + 96)
+    room = max(total, total10, 16)
+    d_out, d_c, d_idx = f.alloc(room), f.alloc(32), f.alloc(4 * n)
+    small = min(n, 2048)
+
+    def capture(d_descs, d_verd, count, snaplen):
+        b = G.DescBatch(w.d_umem.ptr, d_descs.ptr, first, entries - 1, count)
+        return lambda: f.capture_into(b, d_verd.ptr, 1 << 1, d_out.ptr, room, d_c.ptr,
+                                      snaplen=snaplen, stream=sp)
+
+    legs = {"classify": lambda: f.classify_descs(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr,
+                                                 first=first, mask=entries - 1, stream=sp),
+            "compact": lambda: f.compact(w.d_verd.ptr, n, 1, d_idx.ptr, d_c.ptr, stream=sp),
+            "capture": capture(w.d_descs, w.d_verd, n, 0),
+            "capture_1514_snap96_10pct": capture(d_descs10, d_verd10, n, 96),
+            "capture_one_tile": capture(w.d_descs, w.d_verd, small, 0)}
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            call()
+        e0.record(stream)
+        for _ in range(args.iters):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    runs = max(1, args.runs)
+    ms = {k: [] for k in legs}
+    got = {}
+    for _ in range(runs):      # the legs interleaved
+        for k, call in legs.items():
+            ms[k].append(timed(call))
+            got[k] = d_c.download(np.zeros(3, np.uint64)).tolist()
+    assert got["capture"] == [ndrop, total, 0], got["capture"]
+    assert got["capture_1514_snap96_10pct"] == [n10, total10, 0], got
+    probe = min(n * C3D_CHUNK, 1 << 30)
+    f.stream_read_timed(w.d_umem.ptr, probe, 2)
+    read_gbs = probe / (f.stream_read_timed(w.d_umem.ptr, probe, args.iters) * 1e-3) / 1e9
+    # bytes the algorithm moves: a verdict byte a packet; a 16-byte record and
+    # the captured payload (to the dword) of a selected frame read, its block
+    # written
+    moved = {"compact": n + 4 * ndrop,
+             "capture": n + 16 * ndrop + (total - 52 * ndrop) + total,
+             "capture_1514_snap96_10pct": n + 16 * n10 + 96 * n10 + total10}
+    line = {"config": "c3c", "program": f.prog_name, "packets": n, "drop_frames": ndrop,
+            "capture_bytes": total, "selected_10pct": n10, "capture_bytes_10pct": total10,
+            "one_tile_packets": small, "iters": args.iters,
+            "stream_read_GBps": round(read_gbs, 1), "setup_s": round(w.setup_s, 1)}
+    for k in legs:
+        line[k] = {"ms": [round(m, 4) for m in ms[k]]}
+        if k in moved:
+            gbs = moved[k] / (min(ms[k]) * 1e-3) / 1e9
+            line[k].update(bytes=moved[k], GBps=round(gbs, 1),
+                           frac_of_stream_read=round(gbs / read_gbs, 3))
+    line["capture_share_of_classify"] = round(min(ms["capture"]) / min(ms["classify"]), 3)
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
 def run(name, args):
     import numpy as np
     import xftools as X
     import xfgpu as G
     if name == "c1":
         return run_c1(args)
+    if name == "c3c":
+        return run_c3c(args)
     if name == "c3d":
         return run_c3d(args)
     if name == "c3f":

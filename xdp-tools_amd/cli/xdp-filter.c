@@ -537,7 +537,7 @@ static int parse_u32(const char *s, uint32_t max, uint32_t *out)
 
 /* ------------------------------------------------------------------ load */
 enum { O_MODE, O_POLICY, O_FEATURES, O_CAPACITY, O_ALL, O_KEEP, O_REMOVE, O_PROTO, O_STATUS,
-       O_INTERVAL, O_COUNT, O_GPUS, O_DUMP, O_REPEAT, O_QUIET };
+       O_INTERVAL, O_COUNT, O_GPUS, O_DUMP, O_REPEAT, O_QUIET, O_CAPTURE, O_CAPACT, O_SNAPLEN };
 
 static int do_load(int argc, char **argv)
 {
@@ -1080,25 +1080,53 @@ static void *run_shard(void *arg)
 	return NULL;
 }
 
+/* "aborted,drop,pass" -> the action mask of xfg_pcapng_write_captured() */
+static int parse_actions(const char *s, uint32_t *mask)
+{
+	static const char *names[] = { "aborted", "drop", "pass" };
+	*mask = 0;
+	while (*s) {
+		size_t l = strcspn(s, ",");
+		int a = -1;
+		for (int i = 0; i < 3; i++)
+			if (strlen(names[i]) == l && !strncmp(names[i], s, l))
+				a = i;
+		if (a < 0)
+			return -EINVAL;
+		*mask |= 1u << a;
+		s += l;
+		if (*s == ',' && !*++s)
+			return -EINVAL;
+	}
+	return *mask ? 0 : -EINVAL;
+}
+
 static int do_run(int argc, char **argv)
 {
 	static const struct opt opts[] = {
 		{ "gpus", 'g', true, O_GPUS }, { "dump", 'd', true, O_DUMP },
-		{ "repeat", 'n', true, O_REPEAT }, { "quiet", 'q', false, O_QUIET }, { 0, 0, 0, 0 } };
+		{ "repeat", 'n', true, O_REPEAT }, { "quiet", 'q', false, O_QUIET },
+		{ "capture", 'c', true, O_CAPTURE }, { "capture-actions", 'a', true, O_CAPACT },
+		{ "snaplen", 's', true, O_SNAPLEN }, { 0, 0, 0, 0 } };
 	const char *usage =
 		"Usage: xdp-filter run [options] <ifname> <capture>\n"
 		"Classify a pcap/pcapng capture as traffic arriving on <ifname> with the program\n"
 		"loaded there, on the GPUs; hit counters and statistics are updated in the store.\n"
 		"  -g, --gpus <n>            GPUs to shard the capture over (default 1)\n"
 		"  -d, --dump <file>         Write a pcapng with each packet's XDP verdict\n"
+		"  -c, --capture <file>      Write a pcapng of the frames with a verdict in the list\n"
+		"  -a, --capture-actions <l> Verdicts to capture: aborted,drop,pass (default aborted,drop)\n"
+		"  -s, --snaplen <n>         Capture at most n bytes of a frame (default 0: all)\n"
 		"  -n, --repeat <k>          Classify the capture k times (default 1)\n"
 		"  -q, --quiet               No summary line\n";
 	struct args a;
-	uint32_t ngpu = 1, repeat = 1;
+	uint32_t ngpu = 1, repeat = 1, cap_mask = 1u << 0 | 1u << 1, snaplen = 0;
 	int err = parse_args(argc, argv, opts, &a, usage);
 	if (err)
 		return err > 0 ? 0 : 1;
 	if (a.npos != 2 || (a.set[O_GPUS] && (parse_u32(a.val[O_GPUS], 64, &ngpu) || !ngpu)) ||
+	    (a.set[O_CAPACT] && parse_actions(a.val[O_CAPACT], &cap_mask)) ||
+	    (a.set[O_SNAPLEN] && parse_u32(a.val[O_SNAPLEN], 0xffffffffu, &snaplen)) ||
 	    (a.set[O_REPEAT] && (parse_u32(a.val[O_REPEAT], 1u << 20, &repeat) || !repeat))) {
 		pr_warn("Invalid or missing parameter\n%s", usage);
 		return 1;
@@ -1178,6 +1206,12 @@ static int do_run(int argc, char **argv)
 	if (a.set[O_DUMP] &&
 	    (err = xfg_pcapng_write_verdicts(a.val[O_DUMP], ifname, &hb, verdicts))) {
 		pr_warn("Couldn't write %s: %s\n", a.val[O_DUMP], strerror(-err));
+		goto out;
+	}
+	if (a.set[O_CAPTURE] &&
+	    (err = xfg_pcapng_write_captured(a.val[O_CAPTURE], ifname, &hb, verdicts, cap_mask,
+					     snaplen))) {
+		pr_warn("Couldn't write %s: %s\n", a.val[O_CAPTURE], strerror(-err));
 		goto out;
 	}
 	if (!a.set[O_QUIET]) {

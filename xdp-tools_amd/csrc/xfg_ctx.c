@@ -41,6 +41,7 @@ int xfg_launch_compact(const uint8_t *verdicts, uint64_t n, uint32_t action, uin
 		       unsigned grid, void *stream);
 uint64_t xfg_compact_tiles(uint64_t n);
 int xfg_launch_egress(const struct xfg_egress_kargs *a, unsigned grid, void *stream);
+int xfg_launch_capture(const struct xfg_capture_kargs *a, unsigned grid, void *stream);
 int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 		       unsigned long long *hits, uint32_t n, void *stream);
 
@@ -149,7 +150,7 @@ struct xfg_dev {
 	uint32_t log_cw, log_first;
 	uint32_t *rec;                  /* split classify: parse-pass records */
 	uint64_t rec_bytes;
-	unsigned long long *cstatus;    /* verdict compaction, egress: tile status words */
+	unsigned long long *cstatus;    /* verdict compaction, egress, capture: tile status words */
 	uint64_t cstatus_cap;
 	uint32_t *cticket;
 	hipEvent_t ev_user, ev_done;    /* ordering against a caller's stream */
@@ -2273,7 +2274,8 @@ fail:
 }
 
 /* Room for @words status words in the device's tile status buffer (d->lock
- * held, the device current): shared by xfg_compact and xfg_ring_egress, whose
+ * held, the device current): shared by xfg_compact, xfg_ring_egress and the
+ * capture calls, whose
  * launches run one after the other on the device's stream and each zero the
  * words they use first. */
 static int cstatus_room(struct xfg_dev *d, uint64_t words)
@@ -2396,6 +2398,93 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uin
 fail:
 	pthread_mutex_unlock(&d->lock);
 	return err;
+}
+
+/* Capture by verdict (include/xdpfilter_gpu.h): both entry points fill the
+ * kernel's arguments but for the launch's own (state, counts) and come here.
+ * Like xfg_ring_egress it runs on the device's own stream between the two
+ * events, over the same status buffer. */
+static int capture_launch(xfg_ctx *ctx, int dev, struct xfg_capture_kargs *a, uint64_t count,
+			  const struct xfg_capture *c, void *stream)
+{
+	int err = 0;
+	if (!c || c->sz < sizeof(*c) || !c->counts || ((uintptr_t)c->counts & 7) ||
+	    ((uintptr_t)c->ts_ns & 7) || ((uintptr_t)c->out & 15) || (!c->out && c->out_bytes) ||
+	    (!a->verdicts && count) || count > 0xffffffffull)
+		return -EINVAL;
+	if (!ctx->ndev)
+		return -ENODEV;
+	if (dev < 0 || dev >= ctx->ndev)
+		return -EINVAL;
+	if (count && !a->base)
+		return -EINVAL;
+	struct xfg_dev *d = &ctx->dev[dev];
+	hipStream_t user = (hipStream_t)stream;
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!count || !c->action_mask) {   /* no scratch: on the caller's stream itself */
+		HIPCHK(hipMemsetAsync(c->counts, 0, 24, user ? user : d->stream));
+		goto fail;
+	}
+	if ((err = cstatus_room(d, XFG_CAPTURE_STATE_WORDS(count))))
+		goto fail;
+	a->ts_ns = c->ts_ns;
+	a->ts0 = c->ts0;
+	a->out = c->out;
+	a->out_bytes = c->out_bytes;
+	a->counts = (unsigned long long *)c->counts;
+	a->state = d->cstatus;
+	a->n = (uint32_t)count;
+	a->action_mask = c->action_mask;
+	a->snaplen = c->snaplen;
+	if (user && user != d->stream) {
+		HIPCHK(hipEventRecord(d->ev_user, user));
+		HIPCHK(hipStreamWaitEvent(d->stream, d->ev_user, 0));
+	}
+	/* (four workgroups a CU: all of them resident) */
+	err = xfg_launch_capture(a, (unsigned)d->ncu * 4, d->stream);
+	if (!err && user && user != d->stream) {
+		HIPCHK(hipEventRecord(d->ev_done, d->stream));
+		HIPCHK(hipStreamWaitEvent(user, d->ev_done, 0));
+	}
+fail:
+	pthread_mutex_unlock(&d->lock);
+	return err;
+}
+
+int xfg_capture(xfg_ctx *ctx, int dev, const struct xfg_batch *b, const uint8_t *verdicts,
+		const struct xfg_capture *c, void *stream)
+{
+	if (!ctx || !b)
+		return -EINVAL;
+	if (b->count && !b->lens)
+		return -EINVAL;
+	if (!b->offsets && b->count && (b->stride == 0 || (b->stride & 15)))
+		return -EINVAL;
+	if (((uintptr_t)b->data & 15) || ((uintptr_t)b->offsets & 7) ||
+	    ((uintptr_t)b->lens & (b->lens_u16 ? 1 : 3)))
+		return -EINVAL;
+	struct xfg_capture_kargs a = {
+		.base = b->data, .offsets = b->offsets, .lens = b->lens, .verdicts = verdicts,
+		.stride = b->stride, .form = b->lens_u16 ? XFG_CAPTURE_F_LENS_U16 : 0,
+	};
+	return capture_launch(ctx, dev, &a, b->count, c, stream);
+}
+
+int xfg_capture_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+		      const uint8_t *verdicts, const struct xfg_capture *c, void *stream)
+{
+	if (!ctx || !db || !mask_ok(db->mask))
+		return -EINVAL;
+	if (db->count && !db->descs)
+		return -EINVAL;
+	if (((uintptr_t)db->descs & 7) || ((uintptr_t)db->umem & 15))
+		return -EINVAL;
+	struct xfg_capture_kargs a = {
+		.base = db->umem, .descs = db->descs, .verdicts = verdicts,
+		.first = db->first, .mask = db->mask, .form = XFG_CAPTURE_F_DESCS,
+	};
+	return capture_launch(ctx, dev, &a, db->count, c, stream);
 }
 
 /* Achievable streaming-read rate of the device (bench.py roofline leg). */

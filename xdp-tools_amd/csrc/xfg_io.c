@@ -373,73 +373,148 @@ static void w_opt(struct wbuf *w, uint16_t code, const void *p, uint16_t len)
 
 static uint32_t opt_len(size_t len) { return 4 + (((uint32_t)len + 3) & ~3u); }
 
-int xfg_pcapng_write_verdicts(const char *path, const char *ifname,
-			      const struct xfg_host_batch *b, const uint8_t *verdicts)
+/* SHB and IDB of a one-interface section; @snaplen goes into the IDB (0: none) */
+static void w_preamble(struct wbuf *w, const char *ifname, uint32_t snaplen)
 {
-	static const uint8_t zero[4];
 	static const char appl[] = "xdp-filter (MI355X classifier)";
-	if (!path || !b || (!verdicts && b->count))
-		return -EINVAL;
-	struct wbuf w = { fopen(path, "wb"), 0 };
-	if (!w.f)
-		return -errno;
-	setvbuf(w.f, NULL, _IOFBF, 1 << 20);
 	const char *name = ifname ? ifname : "xdp";
 
 	/* SHB: byte-order magic, version 1.0, section length unknown */
 	uint32_t shb_len = 28 + opt_len(sizeof(appl) - 1) + 4;
-	w32(&w, NG_SHB);
-	w32(&w, shb_len);
-	w32(&w, 0x1A2B3C4Du);
-	w16(&w, 1);
-	w16(&w, 0);
+	w32(w, NG_SHB);
+	w32(w, shb_len);
+	w32(w, 0x1A2B3C4Du);
+	w16(w, 1);
+	w16(w, 0);
 	uint64_t seclen = ~0ull;
-	w_raw(&w, &seclen, 8);
-	w_opt(&w, 4, appl, sizeof(appl) - 1);            /* shb_userappl */
-	w32(&w, 0);                                     /* opt_endofopt */
-	w32(&w, shb_len);
+	w_raw(w, &seclen, 8);
+	w_opt(w, 4, appl, sizeof(appl) - 1);            /* shb_userappl */
+	w32(w, 0);                                      /* opt_endofopt */
+	w32(w, shb_len);
 
 	/* IDB: Ethernet, if_name, if_tsresol = 9 (ns) */
 	uint8_t tsres = 9;
 	uint32_t idb_len = 20 + opt_len(strlen(name)) + opt_len(1) + 4;
-	w32(&w, NG_IDB);
-	w32(&w, idb_len);
-	w16(&w, LINKTYPE_ETHERNET);
-	w16(&w, 0);
-	w32(&w, 0);                                     /* snaplen: none */
-	w_opt(&w, 2, name, (uint16_t)strlen(name));     /* if_name */
-	w_opt(&w, 9, &tsres, 1);                        /* if_tsresol */
-	w32(&w, 0);
-	w32(&w, idb_len);
+	w32(w, NG_IDB);
+	w32(w, idb_len);
+	w16(w, LINKTYPE_ETHERNET);
+	w16(w, 0);
+	w32(w, snaplen);
+	w_opt(w, 2, name, (uint16_t)strlen(name));      /* if_name */
+	w_opt(w, 9, &tsres, 1);                         /* if_tsresol */
+	w32(w, 0);
+	w32(w, idb_len);
+}
 
-	/* EPBs with epb_verdict (code 7): type 2 = eBPF XDP, then the u64
-	 * verdict (lib/util/xpcapng.c:155-161, 400-404, 470-474) */
+/* One EPB with epb_verdict (code 7): type 2 = eBPF XDP, then the u64 verdict
+ * (lib/util/xpcapng.c:155-161, 400-404, 470-474) */
+static void w_epb(struct wbuf *w, const uint8_t *frame, uint32_t cap, uint32_t orig, uint64_t ts,
+		  uint8_t verdict)
+{
+	static const uint8_t zero[4];
+	uint8_t vopt[9];
+	uint64_t v = verdict;
+	vopt[0] = 2;
+	memcpy(vopt + 1, &v, 8);
+	uint32_t pad = ((cap + 3) & ~3u) - cap;
+	uint32_t len = 32 + cap + pad + opt_len(sizeof(vopt)) + 4;
+	w32(w, NG_EPB);
+	w32(w, len);
+	w32(w, 0);                              /* interface 0 */
+	w32(w, (uint32_t)(ts >> 32));
+	w32(w, (uint32_t)ts);
+	w32(w, cap);
+	w32(w, orig);
+	w_raw(w, frame, cap);
+	w_raw(w, zero, pad);
+	w_opt(w, 7, vopt, sizeof(vopt));
+	w32(w, 0);
+	w32(w, len);
+}
+
+static int w_open(struct wbuf *w, const char *path, const char *mode)
+{
+	w->f = fopen(path, mode);
+	w->err = 0;
+	if (!w->f)
+		return -errno;
+	setvbuf(w->f, NULL, _IOFBF, 1 << 20);
+	return 0;
+}
+
+static int w_close(struct wbuf *w)
+{
+	if (fclose(w->f) && !w->err)
+		w->err = -EIO;
+	return w->err;
+}
+
+/* The CPU statement of the capture format: xfg_capture_kernel (xfg_capture.hip)
+ * produces these EPB bytes exactly. */
+int xfg_pcapng_write_captured(const char *path, const char *ifname,
+			      const struct xfg_host_batch *b, const uint8_t *verdicts,
+			      uint32_t action_mask, uint32_t snaplen)
+{
+	struct wbuf w;
+	int err;
+	if (!path || !b || (!verdicts && b->count))
+		return -EINVAL;
+	if ((err = w_open(&w, path, "wb")))
+		return err;
+	w_preamble(&w, ifname, snaplen);
 	for (uint64_t i = 0; i < b->count && !w.err; i++) {
+		uint8_t v = verdicts[i];
+		if (v >= 32 || !((action_mask >> v) & 1))
+			continue;
 		uint32_t cap = b->lens[i];
 		uint32_t orig = b->orig_lens ? b->orig_lens[i] : cap;
-		uint64_t ts = b->ts_ns ? b->ts_ns[i] : 0;
-		uint8_t vopt[9];
-		uint64_t v = verdicts[i];
-		vopt[0] = 2;
-		memcpy(vopt + 1, &v, 8);
-		uint32_t pad = ((cap + 3) & ~3u) - cap;
-		uint32_t len = 32 + cap + pad + opt_len(sizeof(vopt)) + 4;
-		w32(&w, NG_EPB);
-		w32(&w, len);
-		w32(&w, 0);                             /* interface 0 */
-		w32(&w, (uint32_t)(ts >> 32));
-		w32(&w, (uint32_t)ts);
-		w32(&w, cap);
-		w32(&w, orig);
-		w_raw(&w, b->data + (b->offsets ? b->offsets[i] : 0), cap);
-		w_raw(&w, zero, pad);
-		w_opt(&w, 7, vopt, sizeof(vopt));
-		w32(&w, 0);
-		w32(&w, len);
+		if (snaplen && cap > snaplen)
+			cap = snaplen;
+		w_epb(&w, b->data + (b->offsets ? b->offsets[i] : 0), cap, orig,
+		      b->ts_ns ? b->ts_ns[i] : 0, v);
 	}
-	if (fclose(w.f) && !w.err)
-		w.err = -EIO;
-	return w.err;
+	return w_close(&w);
+}
+
+int xfg_pcapng_write_verdicts(const char *path, const char *ifname,
+			      const struct xfg_host_batch *b, const uint8_t *verdicts)
+{
+	struct wbuf w;
+	int err;
+	if (!path || !b || (!verdicts && b->count))
+		return -EINVAL;
+	if ((err = w_open(&w, path, "wb")))
+		return err;
+	w_preamble(&w, ifname, 0);
+	for (uint64_t i = 0; i < b->count && !w.err; i++)   /* every frame, whole */
+		w_epb(&w, b->data + (b->offsets ? b->offsets[i] : 0), b->lens[i],
+		      b->orig_lens ? b->orig_lens[i] : b->lens[i], b->ts_ns ? b->ts_ns[i] : 0,
+		      verdicts[i]);
+	return w_close(&w);
+}
+
+int xfg_pcapng_begin(const char *path, const char *ifname, uint32_t snaplen)
+{
+	struct wbuf w;
+	int err;
+	if (!path)
+		return -EINVAL;
+	if ((err = w_open(&w, path, "wb")))
+		return err;
+	w_preamble(&w, ifname, snaplen);
+	return w_close(&w);
+}
+
+int xfg_pcapng_append(const char *path, const void *blocks, uint64_t bytes)
+{
+	struct wbuf w;
+	int err;
+	if (!path || (!blocks && bytes) || (bytes & 3))
+		return -EINVAL;
+	if ((err = w_open(&w, path, "ab")))
+		return err;
+	w_raw(&w, blocks, bytes);
+	return w_close(&w);
 }
 
 /* ------------------------------------------------------------------ rule store */

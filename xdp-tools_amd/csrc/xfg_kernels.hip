@@ -2224,4 +2224,8 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // scheme and status words over 16-byte records
 #include "xfg_egress.hip"
 
+// capture by verdict (pcapng blocks of the selected frames): the same scheme
+// over bytes
+#include "xfg_capture.hip"
+
 #endif   // XFG_PART_COMMON

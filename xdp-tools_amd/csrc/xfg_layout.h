@@ -314,6 +314,36 @@ struct xfg_egress_kargs {
 /* (an even count: the launch's one memset is then a multiple of 16 bytes) */
 #define XFG_EGRESS_STATE_WORDS(n) ((XFG_EGRESS_TILES(n) + 3) & ~1ull)
 
+/* Arguments of the capture kernel (xfg_capture.hip, xfg_capture() and
+ * xfg_capture_descs()): the frames in either batch form, the selection, the
+ * output buffer and the launch's state words laid out as the egress kernel's
+ * (word 0 the tile ticket, from word 2 one {flag, bytes} status word a tile;
+ * zeroed by the launch function together with the three counts). */
+struct xfg_capture_kargs {
+	const uint8_t *base;            /* batch data, or the UMEM */
+	const uint64_t *offsets;        /* batch form: NULL = fixed stride */
+	const void *lens;               /* batch form */
+	const void *descs;              /* descriptor form: struct xdp_desc records */
+	const uint8_t *verdicts;
+	const uint64_t *ts_ns;          /* NULL: ts0 for every frame */
+	uint64_t ts0;
+	uint8_t *out;
+	uint64_t out_bytes;
+	unsigned long long *counts;     /* {blocks written, their bytes, selected not written} */
+	unsigned long long *state;
+	uint32_t n;                     /* packets, >= 1 */
+	uint32_t stride;
+	uint32_t first, mask;           /* descriptor form */
+	uint32_t action_mask;           /* != 0 */
+	uint32_t snaplen;
+	uint32_t form;                  /* XFG_CAPTURE_F_* */
+};
+#define XFG_CAPTURE_F_DESCS 1u
+#define XFG_CAPTURE_F_LENS_U16 2u
+#define XFG_CAPTURE_TILE 2048u   /* packets a tile: 256 lanes x 8 passes */
+#define XFG_CAPTURE_TILES(n) (((uint64_t)(n) + XFG_CAPTURE_TILE - 1) / XFG_CAPTURE_TILE)
+#define XFG_CAPTURE_STATE_WORDS(n) ((XFG_CAPTURE_TILES(n) + 3) & ~1ull)
+
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 #define XFG_HD __host__ __device__ __forceinline__

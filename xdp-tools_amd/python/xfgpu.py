@@ -62,7 +62,7 @@ EXPORTS = [
     "xfg_comm_unique_id", "xfg_comm_init", "xfg_comm_allreduce", "xfg_map_update_batch_percpu",
     "xfg_classify_descs", "xfg_compact", "xfg_classify_xsk_host", "xfg_host_register",
     "xfg_host_unregister", "xfg_last_path", "xfg_host_threads", "xfg_classify_descs_timed",
-    "xfg_ring_egress",
+    "xfg_ring_egress", "xfg_capture", "xfg_capture_descs",
 ]
 EGRESS_SWAP_MACS = 1
 # include/xdpfilter_io.h
@@ -70,7 +70,7 @@ IO_EXPORTS = [
     "xfg_pcap_read", "xfg_host_batch_free", "xfg_pcapng_write_verdicts", "xfg_store_map_name",
     "xfg_store_has_map", "xfg_store_create_map", "xfg_store_remove_map", "xfg_store_map_capacity",
     "xfg_store_load", "xfg_store_save", "xfg_store_stats_read", "xfg_store_stats_write",
-    "xfg_store_stats_remove",
+    "xfg_store_stats_remove", "xfg_pcapng_write_captured", "xfg_pcapng_begin", "xfg_pcapng_append",
 ]
 
 
@@ -106,6 +106,13 @@ class Egress(C.Structure):
                 ("count", C.c_uint64), ("counts", C.c_void_p), ("flags", C.c_uint32)]
 
 
+class Capture(C.Structure):
+    """struct xfg_capture (xfg_capture, xfg_capture_descs)."""
+    _fields_ = [("sz", C.c_size_t), ("action_mask", C.c_uint32), ("snaplen", C.c_uint32),
+                ("ts_ns", C.c_void_p), ("ts0", C.c_uint64), ("out", C.c_void_p),
+                ("out_bytes", C.c_uint64), ("counts", C.c_void_p)]
+
+
 class HostBatch(C.Structure):
     _fields_ = [("data", C.c_void_p), ("offsets", C.POINTER(C.c_uint64)),
                 ("lens", C.POINTER(C.c_uint32)), ("orig_lens", C.POINTER(C.c_uint32)),
@@ -138,6 +145,10 @@ def _load():
         "xfg_host_batch_free": (None, [C.POINTER(HostBatch)]),
         "xfg_pcapng_write_verdicts": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(HostBatch),
                                                 C.POINTER(C.c_uint8)]),
+        "xfg_pcapng_write_captured": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(HostBatch),
+                                                C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]),
+        "xfg_pcapng_begin": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32]),
+        "xfg_pcapng_append": (C.c_int, [C.c_char_p, vp, C.c_uint64]),
         "xfg_store_map_name": (C.c_char_p, [C.c_int]),
         "xfg_store_has_map": (C.c_int, [C.c_char_p, C.c_int]),
         "xfg_store_create_map": (C.c_int, [C.c_char_p, C.c_int, C.c_uint32]),
@@ -159,6 +170,9 @@ def _load():
         "xfg_host_threads": (C.c_int, []),
         "xfg_compact": (C.c_int, [vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp, vp]),
         "xfg_ring_egress": (C.c_int, [vp, C.c_int, C.POINTER(Egress), vp, vp]),
+        "xfg_capture": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.POINTER(Capture), vp]),
+        "xfg_capture_descs": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp, C.POINTER(Capture),
+                                        vp]),
         "xfg_classify_timed": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.c_int,
                                          C.POINTER(C.c_double)]),
         "xfg_classify_descs_timed": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp, C.c_int,
@@ -217,6 +231,47 @@ def read_pcap(path):
         return tuple(out)
     finally:
         lib.xfg_host_batch_free(C.byref(hb))
+
+
+def _host_batch(data, offsets, lens, orig_lens, ts_ns):
+    """struct xfg_host_batch over numpy arrays, and the arrays (kept alive by the caller);
+    orig_lens / ts_ns None: the array is absent (NULL)."""
+    data = np.ascontiguousarray(data, np.uint8)
+    offs = np.ascontiguousarray(offsets, np.uint64)
+    lens = np.ascontiguousarray(lens, np.uint32)
+    ol = None if orig_lens is None else np.ascontiguousarray(orig_lens, np.uint32)
+    ts = None if ts_ns is None else np.ascontiguousarray(ts_ns, np.uint64)
+    hb = HostBatch(data.ctypes.data, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                   lens.ctypes.data_as(C.POINTER(C.c_uint32)),
+                   None if ol is None else ol.ctypes.data_as(C.POINTER(C.c_uint32)),
+                   None if ts is None else ts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                   len(lens), data.nbytes, 1, 0)
+    return hb, (data, offs, lens, ol, ts)
+
+
+def pcapng_write_captured(path, ifname, data, offsets, lens, verdicts, action_mask, snaplen=0,
+                          orig_lens=None, ts_ns=None):
+    """pcapng capture of the frames whose verdict's bit is set in action_mask, cut to
+    snaplen (xfg_pcapng_write_captured)."""
+    hb, keep = _host_batch(data, offsets, lens, orig_lens, ts_ns)
+    v = np.ascontiguousarray(verdicts, np.uint8)
+    _check(lib.xfg_pcapng_write_captured(os.fsencode(path), None if ifname is None else
+                                         ifname.encode(), C.byref(hb),
+                                         v.ctypes.data_as(C.POINTER(C.c_uint8)), action_mask,
+                                         snaplen), "pcapng_write_captured")
+    del keep
+
+
+def pcapng_begin(path, ifname, snaplen=0):
+    """Create or truncate a capture file: its section and interface blocks (xfg_pcapng_begin)."""
+    _check(lib.xfg_pcapng_begin(os.fsencode(path), None if ifname is None else ifname.encode(),
+                                snaplen), "pcapng_begin")
+
+
+def pcapng_append(path, blocks):
+    """Append finished blocks, a capture call's output as it is (xfg_pcapng_append)."""
+    b = blocks if isinstance(blocks, (bytes, bytearray)) else np.ascontiguousarray(blocks).tobytes()
+    _check(lib.xfg_pcapng_append(os.fsencode(path), b, len(b)), "pcapng_append")
 
 
 def write_verdicts_pcapng(path, ifname, data, offsets, lens, verdicts, orig_lens=None, ts_ns=None):
@@ -482,6 +537,45 @@ class Filter:
                    tx_mask, fill_ptr, fill_first, fill_mask, count, counts_ptr, flags)
         _check(lib.xfg_ring_egress(self.ctx, dev, C.byref(e), verdicts_ptr, stream),
                "ring_egress")
+
+    def capture_into(self, batch, verdicts_ptr, action_mask, out_ptr, out_bytes, counts_ptr,
+                     snaplen=0, ts_ns_ptr=None, ts0=0, dev=0, stream=None):
+        """The selected frames of a device batch (a Batch or a DescBatch of device pointers)
+        as pcapng blocks at out_ptr (xfg_capture, xfg_capture_descs); counts_ptr: three u64
+        {blocks written, their bytes, selected frames not written}.  Stream-ordered."""
+        c = Capture(C.sizeof(Capture), action_mask, snaplen, ts_ns_ptr, ts0, out_ptr, out_bytes,
+                    counts_ptr)
+        if isinstance(batch, DescBatch):
+            _check(lib.xfg_capture_descs(self.ctx, dev, C.byref(batch), verdicts_ptr, C.byref(c),
+                                         stream), "capture_descs")
+        else:
+            _check(lib.xfg_capture(self.ctx, dev, C.byref(batch), verdicts_ptr, C.byref(c),
+                                   stream), "capture")
+
+    def capture(self, batch, verdicts, action_mask, snaplen=0, out_bytes=1 << 26, ts_ns=None,
+                ts0=0, dev=0, stream=None):
+        """capture_into() a buffer of out_bytes of its own, then only the counts and the
+        written bytes come back: (blocks: uint8 array of counts[1] bytes, written, lost).
+        batch: a Batch of device pointers; verdicts, ts_ns: device pointers."""
+        room = (max(out_bytes, 16) + 15) & ~15
+        d_out, d_c = self.alloc(room, dev), self.alloc(32, dev)
+        try:
+            self.capture_into(batch, verdicts, action_mask, d_out.ptr if out_bytes else None,
+                              out_bytes, d_c.ptr, snaplen, ts_ns, ts0, dev, stream)
+            self.sync()
+            counts = d_c.download(np.zeros(3, np.uint64))
+            blocks = d_out.download(np.zeros(int(counts[1]), np.uint8))
+        finally:
+            d_out.free()
+            d_c.free()
+        return blocks, int(counts[0]), int(counts[2])
+
+    def capture_descs(self, batch, verdicts, action_mask, snaplen=0, out_bytes=1 << 26, ts_ns=None,
+                      ts0=0, dev=0, stream=None):
+        """capture() of an AF_XDP descriptor batch (a DescBatch of device pointers)."""
+        assert isinstance(batch, DescBatch)
+        return self.capture(batch, verdicts, action_mask, snaplen, out_bytes, ts_ns, ts0, dev,
+                            stream)
 
     def classify_timed(self, data_ptr, lens_ptr, count, stride, verdicts_ptr, iters,
                        offsets_ptr=None, lens_u16=False, dev=0):
