@@ -134,7 +134,7 @@ def test_descs_take_the_pipelined_kernel(G, mixed):
     rules, pool, data, lens = mixed
     all_, eth = X.VARIANT_FEATURES["xdpfilt_dny_all"], X.VARIANT_FEATURES["xdpfilt_dny_eth"]
     # a context opened with the defaults: from XFG_DESCS_PIPE_MIN packets
-    bound = layout_const("XFG_DESCS_PIPE_MIN", "xfg_ctx.c")
+    bound = layout_const("XFG_DESCS_PIPE_MIN", "xfg_plan.h")
     bdata, blens = X.gen_fuzz(32, bound, STRIDE, rules, pool)
     run_case(G, all_, rules, bdata, blens, STRIDE, None, 0, want_path=G.Filter.PATH_PIPELINE,
              descs_min_packets=0)

@@ -26,6 +26,7 @@
 #include <rccl/rccl.h>
 
 #include "xfg_layout.h"
+#include "xfg_plan.h"
 #include "xfg_table.h"
 
 /* from xfg_kernels.hip */
@@ -47,11 +48,6 @@ int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 
 #define NMAPS_HASH 3 /* ipv4, ipv6, ethernet */
 #define XFG_HOST_REG_MAX 16 /* registered host buffers per context */
-/* kernel kinds of the occupancy table (xfg_dev.occ, xfg_classify_occupancy);
- * XFG_OCC_DESCS: the generic pipelined kernel's descriptor instantiation --
- * a kind-1 launch (XFG_PATH_PIPELINE) whose grid is sized from its own entry */
-#define XFG_OCC_KINDS 9
-#define XFG_OCC_DESCS 8
 /* host-resident classify: staging slots in flight (each: a chunk's copies,
  * kernel and verdicts on its own stream; the host prepares the next chunk
  * while the others move) */
@@ -85,15 +81,10 @@ struct xfg_dev {
 	uint32_t *port_nib;             /* XFG_PORT_NIB_WORDS (more ruled ports) */
 	uint32_t port_tab_disp;
 	int port_tab_ok, port_tab_dirty;
-	/* resident classify workgroups per CU: [kernel: 0 general, 1 pipelined,
-	 * 2 pipelined IPv4-key mode, 3 split lookup pass, 4 split parse pass,
-	 * 5 pipelined IPv4-key mode over the quotient index, 6 Ethernet-key]
-	 * [window 64, 128][dynamic LDS: none, direct counters, port nibble map,
-	 * both] */
-	int occ[XFG_OCC_KINDS][2][16];  /* [..][dynamic LDS: + bit 2, the Bloom words (bl_lds);
-			     * + bit 3, the LDS Ethernet key table (xfg_kargs.ek)]; kind 7:
-			     * kind 5 with its count wave (0: cannot launch); kind 8
-			     * (XFG_OCC_DESCS): kind 1's descriptor instantiation */
+	/* resident classify workgroups per CU and threads per workgroup:
+	 * [kernel kind][window 64, 128][dynamic LDS, XFG_OCC_* bits] (xfg_plan.h) */
+	int occ[XFG_OCC_KINDS][2][16];
+	int thr[XFG_OCC_KINDS][2];
 	/* the Ethernet-key kernel's key table (kind 6), uploaded from ctx->ek
 	 * when ek_gen falls behind ctx->ek_gen; params read at launch under
 	 * d->lock */
@@ -201,18 +192,6 @@ struct xfg_ctx {
 	struct { const uint8_t *p; size_t bytes; } reg[XFG_HOST_REG_MAX];
 	int nreg;
 };
-
-/* Default smallest IPv4 map that takes the quotient index (its 2^17 buckets
- * are 4 MiB: below this the canonical table and its prefilter stay in L2). */
-#define XFG_QT_MIN_KEYS (1u << 18)
-/* AF_XDP descriptor batches below this many packets keep the general kernel
- * (xfg_open_opts.descs_min_packets overrides it): on C3's workload as a
- * descriptor batch the pipelined descriptor mode costs 16.7-17.5 us a launch
- * up to 2^16 packets, the general kernel 13.9-14.3 us up to 2^15 and
- * 16.9-17.5 at 2^16; from 2^17 the pipelined mode is ahead (19.1 against
- * 23.5 us; 1.28x at 2^18, 1.79x at 2^22) -- profiles/r07_c3d_ab.log */
-#define XFG_DESCS_PIPE_MIN (1u << 16)
-#define XFG_LOG_PEND_MAX 4u   /* quotient-index launches per count kernel */
 
 /* ------------------------------------------------------------------ misc */
 static const struct { const char *name; uint32_t feat; } prog_table[] = {
@@ -527,13 +506,16 @@ static int dev_init(xfg_ctx *ctx, struct xfg_dev *d)
 	HIPCHK(hipEventCreateWithFlags(&d->ev_done, hipEventDisableTiming));
 
 	for (int k = 0; k < XFG_OCC_KINDS; k++)
-		for (int w = 0; w < 2; w++)
+		for (int w = 0; w < 2; w++) {
+			d->thr[k][w] = xfg_classify_threads(k, w ? 128 : 64);
 			for (int c = 0; c < 16; c++)
 				d->occ[k][w][c] = xfg_classify_occupancy(
 					ctx->prog_features, k, w ? 128 : 64,
-					(c & 1 ? XFG_DCNT_MAX * 4 : 0) + (c & 2 ? XFG_PORT_NIB_WORDS * 4 : 0) +
-					(c & 4 ? XFG_BLOOM_LDS_MAX * 4 : 0) + (c & 8 ? 12 + XFG_EK_SLOTS_MAX * 16 : 0) +
-					(k == 7 ? 16 + XFG_CW_HIST_MAX * 4 : 0));
+					(c & XFG_OCC_DCNT ? XFG_DCNT_MAX * 4 : 0) + (c & XFG_OCC_NIB ? XFG_PORT_NIB_WORDS * 4 : 0) +
+					(c & XFG_OCC_BLOOM ? XFG_BLOOM_LDS_MAX * 4 : 0) +
+					(c & XFG_OCC_EK ? 12 + XFG_EK_SLOTS_MAX * 16 : 0) +
+					(k == XFG_OCC_CW ? 16 + XFG_CW_HIST_MAX * 4 : 0));
+		}
 	/* (a query past the LDS a workgroup can have may leave an error behind:
 	 * not a launch's) */
 	(void)hipGetLastError();
@@ -1383,38 +1365,28 @@ int xfg_map_update_batch_percpu(xfg_ctx *ctx, int map, const void *keys, const u
 }
 
 /* ------------------------------------------------------------------ classify */
-/* Rebuild a device's LDS port image from its flag bytes: the open-addressed
- * table (linear probing from xfg_port_slot()) when at most XFG_PORT_TAB_MAX
- * ports carry flags, else the nibble map of every port's low 4 flag bits
- * (the only ones CHECK_MAP can test). */
-static int port_tab_refresh_locked(struct xfg_dev *d);
-
-
-/* A partition's local-index range of a hit log over @span QT slots. */
-static uint64_t qt_log_hist(uint64_t span)
+/* Device scratch buffer of at least @bytes (grown on demand; the old one may
+ * still be in use by a launch queued on the device stream: wait for it). */
+static int scratch(struct xfg_dev *d, void **p, uint64_t *have, uint64_t bytes)
 {
-	return ((span + 16 * XFG_LOG_PARTS - 1) / (16 * XFG_LOG_PARTS)) * 16;
-}
-
-/* Whether the count kernel covers the hit log of a QT of @span slots: in
- * passes of its LDS histogram (u32 local indices past 65536), or with both
- * lookup directions in one pass (that kernel logs u16 indices only). */
-static int qt_log_fits(uint64_t span, int both)
-{
-	const uint64_t h = qt_log_hist(span);
-	return both ? h <= XFG_LOG_HIST_MAX : h <= (uint64_t)XFG_LOG_HIST_MAX * XFG_LOG_PASSES_MAX;
-}
-
-static int port_tab_refresh(struct xfg_dev *d)
-{
-	/* (under the device lock: launch_batch reads the image's kind and
-	 * displacement there; lock order ctx->lock, then d->lock) */
-	pthread_mutex_lock(&d->lock);
-	int err = port_tab_refresh_locked(d);
-	pthread_mutex_unlock(&d->lock);
+	if (bytes <= *have)
+		return 0;
+	int err = hip_err(hipStreamSynchronize(d->stream));
+	if (err)
+		return err;
+	hipFree(*p);
+	*p = NULL;
+	*have = 0;
+	err = hip_err(hipMalloc(p, bytes));
+	if (!err)
+		*have = bytes;
 	return err;
 }
 
+/* Rebuild a device's LDS port image from its flag bytes (d->lock held): the
+ * open-addressed table (linear probing from xfg_port_slot()) when at most
+ * XFG_PORT_TAB_MAX ports carry flags, else the nibble map of every port's
+ * low 4 flag bits (the only ones CHECK_MAP can test). */
 static int port_tab_refresh_locked(struct xfg_dev *d)
 {
 	uint32_t tab[XFG_PORT_TAB];
@@ -1451,7 +1423,15 @@ static int port_tab_refresh_locked(struct xfg_dev *d)
 	return err;
 }
 
-static int scratch(struct xfg_dev *d, void **p, uint64_t *have, uint64_t bytes);
+static int port_tab_refresh(struct xfg_dev *d)
+{
+	/* (under the device lock: launch_batch reads the image's kind and
+	 * displacement there; lock order ctx->lock, then d->lock) */
+	pthread_mutex_lock(&d->lock);
+	int err = port_tab_refresh_locked(d);
+	pthread_mutex_unlock(&d->lock);
+	return err;
+}
 
 /* Bring the quotient index of the IPv4 map up to date for lookups of mask
  * @live (ctx->lock held): rebuild the host image when the map changed, then
@@ -1543,35 +1523,68 @@ static int ek_refresh(xfg_ctx *ctx, struct xfg_dev *d)
 	return err;
 }
 
-/* @db: the AF_XDP descriptors of the batch (xfg_classify_descs: @b then
- * carries the UMEM and the count, no lengths and no stride), or NULL */
-static int fill_kargs_src(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b,
-			  const struct xfg_desc_batch *db, uint8_t *verdicts, struct xfg_kargs *a)
+/* One classify call between its two lock sections: the kernel arguments
+ * the snapshot fills (the plan's follow in launch_batch) and the plan's
+ * input. */
+struct launch {
+	struct xfg_kargs a;
+	struct xfg_plan_in in;
+	struct xfg_knobs knobs;
+};
+
+#ifdef XFG_DIAG
+/* The measurement knobs (xfg_plan.h) from the environment, at every launch. */
+static const struct xfg_knobs *knobs_read(struct xfg_knobs *k)
 {
+	xfg_knobs_init(k);
+	for (const char *const *n = xfg_knob_names; *n; n++) {
+		const char *v = getenv(*n);
+		if (v)
+			xfg_knobs_set(k, *n, v);
+	}
+	return k;
+}
+#else
+#define knobs_read(k) NULL
+#endif
+
+/* Under ctx->lock: the census and the table descriptors as the batch's
+ * launch will see them, and the device's images the plan asks for brought
+ * up to date.  @db: the AF_XDP descriptors of the batch (@b then carries the
+ * UMEM and the count, no lengths and no stride), or NULL; @hwin: a
+ * header-window batch of the host path. */
+static int snapshot(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b,
+		    const struct xfg_desc_batch *db, uint8_t *verdicts, int hwin, struct launch *l)
+{
+	struct xfg_kargs *a = &l->a;
+	struct xfg_plan_in *in = &l->in;
 	memset(a, 0, sizeof(*a));
+	memset(in, 0, sizeof(*in));
+	pthread_mutex_lock(&ctx->lock);
+	ctx->reduced = 0;
 	int err = port_tab_refresh(d);
 	if (err)
-		return err;
+		goto out;
 	struct xfg_tdesc *td[NMAPS_HASH] = { &a->t4, &a->t6, &a->te };
+	uint64_t gb = 0;
 	for (int i = 0; i < NMAPS_HASH; i++) {
 		xfg_table_desc(&ctx->t[i], td[i]);
 		td[i]->buckets = d->m[i].buckets;
 		td[i]->bloom = d->m[i].bloom;
 		td[i]->hits = d->m[i].hits;
 		td[i]->fmask = census_mask(ctx->flag_cnt[i]);
-	}
-	a->port_fmask = census_mask(ctx->port_flag_cnt);
-	uint64_t gb = 0;
-	for (int i = 0; i < NMAPS_HASH; i++) {
 		a->gbase[i] = (uint32_t)gb;
 		gb += (uint64_t)ctx->t[i].nslots + 1;
+		in->map[i].count = td[i]->count;
+		in->map[i].fmask = td[i]->fmask;
+		in->map[i].bloom_words = td[i]->bloom_words;
+		in->map[i].nslots = td[i]->nslots;
 	}
 	a->gbase[3] = (uint32_t)gb;
+	a->port_fmask = census_mask(ctx->port_flag_cnt);
 	a->port_hits = d->port_hits;
 	a->port_count = ctx->port_count;
-	a->port_tab = d->port_tab_ok ? d->port_tab : NULL;
 	a->port_nib = d->port_nib;
-	a->port_tab_disp = d->port_tab_disp;
 	a->stats = d->stats;
 	a->data = b->data;
 	a->offsets = b->offsets;
@@ -1580,549 +1593,235 @@ static int fill_kargs_src(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batc
 	a->stride = b->stride;
 	a->lens_u16 = b->lens_u16;
 	a->verdicts = verdicts;
-	/* Header window: 64 bytes for fixed strides (a parse that reaches past
-	 * it -- IPv6/TCP's doff at byte 66, long IPv6 extension chains -- is a
-	 * deferred walk over the frame in HBM), unless the context asked for
-	 * 128 (xfg_open_opts.window: such frames then stay on the fast path);
-	 * frames at offsets stage 128 bytes in the general kernel.  On C4/C5's
-	 * 1536-byte slots the 64-byte window was 14 % faster (r04 session 16). */
-	a->window = (!b->offsets && b->stride && (b->stride <= 64 || ctx->window == 64)) ? 64 : 128;
-#ifdef XFG_DIAG
-	const char *wn = getenv("XFG_WINDOW");   /* "64" / "128" above a 64-byte stride */
-	if (wn && !strcmp(wn, "64") && !b->offsets && b->stride)
-		a->window = 64;
-	else if (wn && !strcmp(wn, "128") && b->stride > 64)
-		a->window = 128;
-#endif
-	/* The pipelined kernel takes every fixed-stride batch whose windows can
-	 * be loaded without a length (stride >= window, 16-byte aligned; packet
-	 * indices fit its 32-bit deferred lists); the general kernel the rest. */
-	a->pipe = !b->offsets && b->stride >= a->window && !(b->stride & 15) &&
-		  !((uintptr_t)b->data & 15) && b->count < (1ull << 32) && b->stride < 65536;
-	const int ek_only = !(ctx->prog_features & (XFG_FEAT_IPV4 | XFG_FEAT_IPV6 | XFG_FEAT_TCP | XFG_FEAT_UDP));
+	a->hwin = hwin;
 	if (db) {
-		/* AF_XDP descriptors: the generic pipelined kernel's descriptor
-		 * mode (xfg_pipeline.hip, SRC_DESCS; 32-bit packet indices) with the
-		 * context's window -- and no other pipelined kernel: key mode 0
-		 * whatever the census says, no quotient index (below).  The
-		 * Ethernet-only programs' pipelined kernel is the Ethernet-key one,
-		 * which reads fixed-stride slots: their descriptor batches keep the
-		 * general kernel, with the 128-byte window it always had there; so
-		 * do batches below XFG_DESCS_PIPE_MIN packets (above: the
-		 * general kernel's lower fixed cost wins there). */
 		a->descs = db->descs;
 		a->desc_mask = db->mask;
 		a->desc_first = db->first;
-		a->pipe = !ek_only && b->count < (1ull << 32) && b->count >= ctx->descs_min;
 	}
-#ifdef XFG_DIAG
-	const char *ks = getenv("XFG_KERNEL");   /* diagnostics build only */
-	if (ks && !strcmp(ks, "general"))
-		a->pipe = 0;
-#endif
-	if (db)
-		a->window = a->pipe ? ctx->window : 128;
-	a->dense = a->pipe && a->stride == a->window;
-	/* key mode 1: no Ethernet or IPv6 lookup can hit (flag census), so the
-	 * pipelined kernel carries IPv4 keys only */
-	int eth_live = (ctx->prog_features & XFG_FEAT_ETHERNET) && a->te.count && (a->te.fmask & 3);
-	int v6_live = (ctx->prog_features & XFG_FEAT_IPV6) && a->t6.count && (a->t6.fmask & 3);
-	a->km = !db && (ctx->prog_features & XFG_FEAT_IPV4) && !eth_live && !v6_live;
-	/* (IPv6 keys live, Ethernet keys not: the quotient-index kernel may still
-	 * take the batch, sending every IPv6 frame to its deferred path) */
-	const int km6 = !db && (ctx->prog_features & XFG_FEAT_IPV4) && !eth_live && v6_live;
-	a->v6d = 0;
-	int kgen = 0;
-#ifdef XFG_DIAG
-	/* "generic": key mode 0 whatever the census says -- the generic
-	 * pipelined kernel on a batch the IPv4-key kernels would take (the
-	 * strided figure beside a descriptor batch's, tools/bench_configs.py c3d) */
-	kgen = ks && !strcmp(ks, "generic");
-	if (kgen)
-		a->km = 0;
-#endif
-	/* per-lane u32 byte sums in the pipelined kernel: bound them (the
-	 * descriptor mode sums in 64 bits: its lengths are not the host's to see) */
-	if (!db && a->pipe && (uint64_t)a->stride * (((b->count + 63) / 64 + 1023) / 1024 + 1) >= (1ull << 32))
-		a->pipe = 0;
-#ifdef XFG_DIAG
-	const char *dm = getenv("XFG_DIAG_MASK");   /* pipelined IPv4-key kernel: drop a cost */
-	if (dm && *dm)
-		a->diag = (uint32_t)strtoul(dm, NULL, 0);
-	const char *tsp = getenv("XFG_TSTAMP");   /* device buffer for the QT kernel's phase stamps */
-	if (tsp && *tsp)
-		a->tstamp = (unsigned long long *)(uintptr_t)strtoull(tsp, NULL, 0);
-	const char *kk = getenv("XFG_KERNEL");   /* "split": parse + lookup passes */
-	if (kk && !strcmp(kk, "split"))
-		a->split = a->pipe && a->km;   /* (km 0 with descriptors: never) */
-	const char *bo = getenv("XFG_BLOOM");    /* "off": lookup pass without the prefilter */
-	if (bo && !strcmp(bo, "off") && !(a->t4.count && (a->t4.fmask & 3) == 3))
-		a->bloom_off = 1;
-	const char *em = getenv("XFG_EMPTY");   /* every table empty: stream + parse only */
-	if (em && !strcmp(em, "1")) {
-		a->t4.count = a->t6.count = a->te.count = 0;
-		a->port_count = 0;
-	}
-#endif
-	/* the Ethernet-key kernel (kind 6): the Ethernet-only programs, their
-	 * map as an LDS key table -- every lookup answered in LDS, no frame
-	 * byte past the two addresses read */
-	/* (and, since round 6, for the generic pipelined kernel -- live
-	 * Ethernet keys beside IP keys: dny_all / alw_all with a few MAC rules --
-	 * which answers both Ethernet lookups from the same table in LDS) */
-	int ek = a->pipe && (ctx->prog_features & XFG_FEAT_ETHERNET) && (ek_only || eth_live);
-#ifdef XFG_DIAG
-	const char *eo = getenv("XFG_EK");   /* "off": the generic pipelined kernel */
-	if (eo && !strcmp(eo, "off"))
-		ek = 0;
-#endif
-	if (ek) {
-		if ((err = ek_refresh(ctx, d)))
-			return err;
-		if (ctx->ek_ok)
-			a->ek = d->ek_img;   /* (parameters: launch_batch, under d->lock) */
-	}
-	/* (live Ethernet keys, no IPv6 key, the Ethernet map as the LDS key
-	 * table: the quotient-index kernel answers the Ethernet lookups from
-	 * the table ahead of its IPv4 lookups -- since round 6; else the
-	 * generic pipelined kernel takes the batch) */
-	const int kme = !db && (ctx->prog_features & XFG_FEAT_IPV4) && eth_live && !v6_live && a->ek && !ek_only;
-	/* the quotient index (kind 5 kernel): the IPv4-key kernel with one or
-	 * both IPv4 lookup directions live, the same flags on every device, and
-	 * a map large enough that the prefilter + bucket-line chain leaves L2;
-	 * its hit log must fit the count kernel's histogram */
-	if (a->pipe && !kgen && (a->km || km6 || kme) && !a->split) {
-		/* (both directions live: up to two images, twice the QT slots) */
-		const int dl = a->t4.count && (a->t4.fmask & 2), sl = a->t4.count && (a->t4.fmask & 1);
-		const int ok = (dl | sl) && !ctx->flag_cnt[0][7] &&
-			       qt_log_fits(((uint64_t)XFG_QT_SLOTS << xfg_qt_bits_for(a->t4.count)) << (dl & sl),
-					   dl & sl);
-		int use = ok && a->t4.count >= ctx->qt_min_keys;
-#ifdef XFG_DIAG
-		const char *qo = getenv("XFG_QT");   /* "off" / "on" (any size) */
-		if (qo && !strcmp(qo, "off"))
-			use = 0;
-		else if (qo && !strcmp(qo, "on"))
-			use = ok;
-#endif
-		if (use) {
-			int err2 = qt_refresh(ctx, d, (dl ? 2u : 0u) | (sl ? 1u : 0u));
-			if (err2)
-				return err2;
-			a->qt = d->qt_img;   /* (parameters: launch_batch, under d->lock) */
-			if (!a->km) {
-				a->km = 1;
-				a->v6d = !kme;
-			}
+	in->feat = ctx->prog_features;
+	in->flags_differ4 = ctx->flag_cnt[0][7];
+	in->port_count = ctx->port_count;
+	in->ctx_window = ctx->window;
+	in->qt_min_keys = ctx->qt_min_keys;
+	in->descs_min = ctx->descs_min;
+	in->n = b->count;
+	in->stride = b->stride;
+	in->offsets = b->offsets != NULL;
+	in->aligned16 = !((uintptr_t)b->data & 15);
+	in->descs = db != NULL;
+	in->hwin = hwin;
+	in->ncu = d->ncu;
+	in->occ = d->occ;
+	in->thr = d->thr;
+	in->knobs = knobs_read(&l->knobs);
+	if (in->knobs) {
+		a->diag = in->knobs->diag_mask;
+		a->tstamp = (unsigned long long *)(uintptr_t)in->knobs->tstamp;
+		if (in->knobs->empty) {
+			a->t4.count = a->t6.count = a->te.count = 0;
+			a->port_count = 0;
 		}
 	}
-	return 0;
-}
-
-static int fill_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *b,
-		      uint8_t *verdicts, struct xfg_kargs *a)
-{
-	return fill_kargs_src(ctx, d, b, NULL, verdicts, a);
-}
-
-/* Device scratch buffer of at least @bytes (grown on demand; the old one may
- * still be in use by a launch queued on the device stream: wait for it). */
-static int scratch(struct xfg_dev *d, void **p, uint64_t *have, uint64_t bytes)
-{
-	if (bytes <= *have)
-		return 0;
-	int err = hip_err(hipStreamSynchronize(d->stream));
-	if (err)
-		return err;
-	hipFree(*p);
-	*p = NULL;
-	*have = 0;
-	err = hip_err(hipMalloc(p, bytes));
-	if (!err)
-		*have = bytes;
+	struct xfg_wants w;
+	xfg_plan_wants(in, &w);
+	if (w.ek) {
+		if ((err = ek_refresh(ctx, d)))
+			goto out;
+		in->ek_ok = ctx->ek_ok;
+		xfg_plan_wants(in, &w);
+	}
+	if (w.qt_live)
+		err = qt_refresh(ctx, d, w.qt_live);
+out:
+	pthread_mutex_unlock(&ctx->lock);
 	return err;
+}
+
+/* Work on the device's own stream between a caller's: after what @user (a
+ * caller's stream; NULL or the device's own: nothing to order) holds ... */
+static int stream_enter(struct xfg_dev *d, void *user)
+{
+	if (!user || user == (void *)d->stream)
+		return 0;
+	int err = hip_err(hipEventRecord(d->ev_user, (hipStream_t)user));
+	return err ? err : hip_err(hipStreamWaitEvent(d->stream, d->ev_user, 0));
+}
+
+/* ... and @user's later work after it. */
+static int stream_leave(struct xfg_dev *d, void *user)
+{
+	if (!user || user == (void *)d->stream)
+		return 0;
+	int err = hip_err(hipEventRecord(d->ev_done, d->stream));
+	return err ? err : hip_err(hipStreamWaitEvent((hipStream_t)user, d->ev_done, 0));
 }
 
 /* classify launches on the device's own stream (every classify of a device
  * is serialised there), ordered after and before @user (a caller's stream,
- * or NULL).  The per-launch scratch (hit log, deferred lists) is sized and
- * used under the device lock, so concurrent callers never see a buffer
- * being replaced. */
-static int launch_batch(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_kargs *a0,
-			void *user, int iters)
+ * or NULL).  Under the device lock: the plan from the device's images in
+ * stream order at this launch, the per-launch scratch (hit log, deferred
+ * lists) sized and used, so concurrent callers never see a buffer being
+ * replaced. */
+static int launch_batch(xfg_ctx *ctx, struct xfg_dev *d, struct launch *l, void *user, int iters)
 {
 	int err = 0;
-	struct xfg_kargs a = *a0;
-	const char *cm = NULL;
-	int nolog = 0;   /* (diagnostics: every kernel without the hit log) */
-#ifdef XFG_DIAG
-	cm = getenv("XFG_COUNT");   /* diagnostics build only: "atomic" */
-	if (cm && !strcmp(cm, "atomic"))
-		a.qt = NULL;             /* (the QT kernel's counting is the log, or no log) */
-	const char *lg = getenv("XFG_LOG");   /* "off": counters by LDS cache + atomics */
-	nolog = lg && !strcmp(lg, "off");
-#endif
-	/* small rule sets: a direct LDS counter per hash-map slot (their few
-	 * counters are hot: more than the LDS counter cache holds) */
-	if (a.gbase[3] <= XFG_DCNT_MAX)
-		a.dcnt = a.gbase[3];       /* every hash-map counter */
-	else if (a.gbase[1] <= XFG_DCNT_MAX)
-		a.dcnt = a.gbase[1];       /* the IPv4 map's counters */
+	struct xfg_kargs *a = &l->a;
+	struct xfg_plan_in *in = &l->in;
+	struct xfg_plan p;
 	pthread_mutex_lock(&d->lock);
-	/* the port image in stream order at this launch (another caller's
-	 * port_tab_refresh may have rewritten it since fill_kargs; both hold
-	 * d->lock for that): its kind and its longest displacement */
-	a.port_tab = d->port_tab_ok ? d->port_tab : NULL;
-	a.port_tab_disp = d->port_tab_disp;
-	/* the hit log (below) decides whether the quotient-index kernel can run:
-	 * it counts through the log only.  Where the log cannot be set up (every
-	 * counter has a direct LDS counter, or the grid has more workgroups than
-	 * the log has slices) the IPv4-key kernel takes the batch instead. */
-	/* (a few keys in all -- C1's 8 MAC rules -- are hot: the LDS counter
-	 * cache holds every one of them, where the log would send their hits
-	 * through a handful of overfull partitions to contended atomics) */
-	const uint64_t nkeys = (uint64_t)a.t4.count + a.t6.count + a.te.count;
-	const int logged = nkeys > XFG_LOG_MIN_KEYS;
-	/* (the Ethernet-key kernel -- the Ethernet-only programs -- counts in LDS;
-	 * the generic kernel with the LDS key table logs its IP hits as usual) */
-	const int ek_only = a.pipe && a.ek && !(ctx->prog_features & (XFG_FEAT_IPV4 | XFG_FEAT_IPV6 | XFG_FEAT_TCP | XFG_FEAT_UDP));
-	const int log_no = !a.pipe || !logged || a.dcnt >= a.gbase[3] || ek_only || (cm && !strcmp(cm, "atomic"));
-	/* (a batch of fewer packets than counters: the count kernel's pass over
-	 * every counter costs more than the atomics it saves -- C5's 15M + 1M
-	 * rules at 2^23 packets: 0.45 ms with atomics, 0.65-0.71 with the log;
-	 * C4's 1M at 2^23 and C3's at 2^24 and 2^26 keep the log, r04 sessions
-	 * 16 and 18) */
-	int qt_nolog = 0;
-	if (a.qt) {
-		const int k5 = 5, wi5 = a.window > 64;
-		const int pc = d->occ[k5][wi5][(a.dcnt > 0) | (!a.port_tab && a.port_count ? 2 : 0) | (a.bl_lds ? 4 : 0) |
-					      (a.ek ? 8 : 0)];
-		const uint64_t pw = (uint64_t)xfg_classify_threads(k5, a.window);
-		uint64_t g5 = (uint64_t)d->ncu * (pc > 0 ? pc : 1), need5 = (a.n + pw - 1) / pw;
-		if (g5 > need5)
-			g5 = need5 ? need5 : 1;
-		/* (a log the count kernel cannot take: the index kernel counts
-		 * through its LDS counter cache and atomics instead) */
-		if (log_no)
-			a.qt = NULL;
-		/* (with the count wave the log's count costs the launch nothing:
-		 * then the log from XFG_CW_LOG_MIN packets instead of twice the
-		 * QT slots -- the atomics it saves are the slow part at C4's
-		 * per-GPU shard of 2^21 packets) */
-		const int occ_c5 = (a.dcnt > 0) | (!a.port_tab && a.port_count ? 2 : 0);
-		const int cw_cap = qt_log_hist(d->qt_n) <= XFG_CW_HIST_MAX && a.window <= 64 && !a.v6d && !a.ek &&
-				   2 * g5 <= XFG_LOG_SLICES_MAX && d->occ[7][0][occ_c5] > 0;
-		uint64_t cw_min = XFG_CW_LOG_MIN;
-#ifdef XFG_DIAG
-		const char *cm2 = getenv("XFG_CW_LOG_MIN");   /* packets from which the count wave's log runs */
-		if (cm2 && *cm2)
-			cw_min = strtoull(cm2, NULL, 0);
-		const char *cwo = getenv("XFG_CW");
-		if (cwo && !strcmp(cwo, "off"))
-			cw_min = ~0ull;
-#endif
-		if (nolog || g5 > XFG_LOG_SLICES_MAX || !qt_log_fits(d->qt_n, d->qt_live == 3) ||
-		    (2 * (uint64_t)d->qt_n > a.n && !(cw_cap && a.n >= cw_min)))
-			qt_nolog = 1;
-		/* (the log from twice as many packets as QT slots: at as many, C3's
-		 * and C4's 1M rules at 2^21 packets ran 0.068 / 0.088 ms with it and
-		 * 0.060 / 0.080 without; at twice, the same; at four times, the log
-		 * 10 % faster -- profiles/archive/r05_s39_session.log) */
+	/* (another caller's refresh may have rewritten the images since the
+	 * snapshot; both hold d->lock for that) */
+	in->port_tab_ok = d->port_tab_ok;
+	in->qt_n = d->qt_n;
+	in->qt_live = d->qt_live;
+	in->qt_nimg = d->qt_nimg;
+	in->qt_bits = d->qt_bits;
+	in->ek_slots = d->ek_slots;
+	xfg_plan(in, &p);
+	const uint64_t grid = p.grid;
+	a->port_tab = d->port_tab_ok ? d->port_tab : NULL;
+	a->port_tab_disp = d->port_tab_disp;
+	a->window = p.window;
+	a->pipe = p.pipe;
+	a->dense = p.dense;
+	a->km = p.km;
+	a->v6d = p.v6d;
+	a->v6p = p.v6p;
+	a->split = p.split;
+	a->bloom_off = p.bloom_off;
+	a->grid_parse = p.grid_parse;
+	a->dcnt = p.dcnt;
+	a->bl_lds = p.bl_lds;
+	memcpy(a->bl_off, p.bl_off, sizeof(a->bl_off));
+	a->qt_dyn = p.qt_dyn;
+	if (p.use_ek) {
+		a->ek = d->ek_img;
+		a->ek_slots = d->ek_slots;
+		a->ek_disp = d->ek_disp;
 	}
-	const int log_off = log_no || nolog ||
-			    (!a.qt && (uint64_t)a.gbase[3] + XFG_PORT_MAP_ENTRIES > a.n);
-	if (!a.qt && a.v6d) {   /* (the IPv6 keys need the general kernel then) */
-		a.km = 0;
-		a.v6d = 0;
-	}
-	/* the generic pipelined kernel: small maps' Bloom filters staged in LDS */
-	a.bl_lds = 0;
-	if (!a.pipe)   /* (header windows of the host path: the general kernel) */
-		a.ek = NULL;
-	if (a.ek) {   /* the key table in stream order at this launch */
-		a.ek = d->ek_img;
-		a.ek_slots = d->ek_slots;
-		a.ek_disp = d->ek_disp;
-	}
-	if (a.pipe && !a.km && !ek_only) {
-		const struct xfg_tdesc *tt[3] = { &a.t4, &a.te, &a.t6 };
-		uint32_t tot = 0;
-		for (int i = 0; i < 3; i++) {
-			a.bl_off[i] = ~0u;
-			/* (the LDS key table answers the Ethernet lookups) */
-			if (tt[i]->count && tt[i]->bloom_words && !(i == 1 && a.ek)) {
-				a.bl_off[i] = tot;
-				tot += tt[i]->bloom_words;
-			}
-		}
-		if (tot <= XFG_BLOOM_LDS_MAX)
-			a.bl_lds = tot;
-#ifdef XFG_DIAG
-		const char *bl = getenv("XFG_BLOOM_LDS");   /* "off": the words from memory */
-		if (bl && !strcmp(bl, "off"))
-			a.bl_lds = 0;
-#endif
-	}
-	const int kind = ek_only ? 6 : a.pipe ? (a.km ? (a.split ? 3 : (a.qt ? 5 : 2)) : 1) : 0, wi = a.window > 64;
-	if (a.qt) {   /* the index in stream order at this launch */
-		a.qt = d->qt_img;
-		a.qt_trans = d->qt_trans;
-		a.qt_bits = d->qt_bits;
-		a.qt_seed = d->qt_seed;
-		a.qt_live = d->qt_live;
-		a.qt_n = d->qt_n;
+	if (p.use_qt) {
+		a->qt = d->qt_img;
+		a->qt_trans = d->qt_trans;
+		a->qt_bits = d->qt_bits;
+		a->qt_seed = d->qt_seed;
+		a->qt_live = d->qt_live;
+		a->qt_n = d->qt_n;
 		/* the second (src) lookup's image and its slots' offset: the same
 		 * image at offset 0 when one serves both directions */
-		a.qt_base = d->qt_nimg == 2 ? d->qt_n / 2 : 0;
-		a.qt2 = d->qt_img + (uint64_t)a.qt_base * 2 / 4;
+		a->qt_base = d->qt_nimg == 2 ? d->qt_n / 2 : 0;
+		a->qt2 = d->qt_img + (uint64_t)a->qt_base * 2 / 4;
 		/* its QT-order counts (zeroed when (re)allocated; a resize only
 		 * follows a fold: qt_refresh) */
-		/* (two halves: the log's counts, the atomics' -- xfg_kargs.qt_hitx) */
-		const uint64_t qb = (uint64_t)d->qt_n * 8, had = d->qt_hits_bytes;
-		if ((err = scratch(d, (void **)&d->qt_hits, &d->qt_hits_bytes, qb)))
+		const uint64_t had = d->qt_hits_bytes;
+		if ((err = scratch(d, (void **)&d->qt_hits, &d->qt_hits_bytes, p.bytes.qt_hits)))
 			goto out;
 		if (d->qt_hits_bytes != had &&
 		    (err = hip_err(hipMemsetAsync(d->qt_hits, 0, d->qt_hits_bytes, d->stream))))
 			goto out;
-		a.qt_hits = d->qt_hits;
-		a.qt_hitx = d->qt_hits + d->qt_n;
+		a->qt_hits = d->qt_hits;
+		a->qt_hitx = d->qt_hits + d->qt_n;
 	}
-	/* (the descriptor instantiation of kind 1: its own occupancy entry) */
-	int per_cu = d->occ[kind == 1 && a.descs ? XFG_OCC_DESCS : kind][wi][(a.dcnt > 0) | (!a.port_tab && a.port_count ? 2 : 0) |
-				     (a.bl_lds ? 4 : 0) | (a.ek ? 8 : 0)];
-#ifdef XFG_DIAG
-	const char *g = getenv("XFG_GRID_PER_CU");
-	if (g && *g)
-		per_cu = (int)strtol(g, NULL, 0);
-#endif
-	const uint64_t per_wg = (uint64_t)xfg_classify_threads(kind, a.window);
-	uint64_t grid = (uint64_t)d->ncu * (per_cu > 0 ? per_cu : 1);
-	uint64_t need = (a.n + per_wg - 1) / per_wg;
-	if (grid > need)
-		grid = need ? need : 1;
-
-	if (a.split) {
-		/* the parse pass: its own persistent grid */
-		uint64_t gp = (uint64_t)d->ncu * (d->occ[4][wi][0] > 0 ? d->occ[4][wi][0] : 1);
-		uint64_t tpw = (uint64_t)xfg_classify_threads(4, a.window);   /* packets per round */
-		uint64_t np = (a.n + tpw - 1) / tpw;
-		a.grid_parse = (uint32_t)(gp < np ? gp : (np ? np : 1));
-	}
-
-	if (a.split) {
-		/* parse-pass records: key a, ports, key b (both directions live) */
-		int both = a.t4.count && (a.t4.fmask & 3) == 3;
-		uint64_t per = (uint64_t)a.n * 4;
-		if ((err = scratch(d, (void **)&d->rec, &d->rec_bytes, per * (both ? 3 : 2))))
+	if (p.split) {
+		if ((err = scratch(d, (void **)&d->rec, &d->rec_bytes, p.bytes.rec)))
 			goto out;
-		a.rec_ka = d->rec;
-		a.rec_port = d->rec + a.n;
-		a.rec_kb = both ? d->rec + 2 * a.n : NULL;
+		a->rec_ka = d->rec;
+		a->rec_port = d->rec + a->n;
+		a->rec_kb = p.rec_both ? d->rec + 2 * a->n : NULL;
 	}
-	if (a.pipe && !ek_only) {   /* (the Ethernet-key kernel defers nothing) */
-		/* one deferred list per wave, room for every packet of its tiles --
-		 * a quarter more than a fixed share: the quotient-index kernel's
-		 * waves take their workgroup's tiles as they go (XFG_QT_DYN), at
-		 * most defer_cap / 64 each */
-		uint64_t nw = grid * (per_wg / 64), nt = (a.n + 63) / 64;
-		uint64_t per = (nt + nw - 1) / nw;
-		uint64_t cap = (per + per / 4 + 2) * 64;
-		if ((err = scratch(d, (void **)&d->defer, &d->defer_bytes, nw * cap * 4)))
+	if (p.bytes.defer) {
+		if ((err = scratch(d, (void **)&d->defer, &d->defer_bytes, p.bytes.defer)))
 			goto out;
-		a.defer = d->defer;
-		a.defer_cap = (uint32_t)cap;
-		/* (diagnostics: the quotient-index kernel lists its deferred
-		 * packets for xfg_defer_kernel, two workgroups a CU over every
-		 * list -- 1-3 % slower than each wave's own tail on C3 and C5,
-		 * r04 session 19) */
-		int sep = 0;
-#ifdef XFG_DIAG
-		const char *dfe = getenv("XFG_DEFER");   /* "kernel" */
-		sep = dfe && !strcmp(dfe, "kernel") && kind == 5 && nw <= XFG_DEFER_SRC_MAX;
-#endif
-		if (sep) {
-			if ((err = scratch(d, (void **)&d->defer_n, &d->defer_n_bytes, nw * 4)))
-				goto out;
-			a.defer_n = d->defer_n;
-			a.defer_nsrc = (uint32_t)nw;
-			a.defer_sep = 1;
-			a.defer_grid = (uint32_t)d->ncu * 2;
-		}
+		a->defer = d->defer;
+		a->defer_cap = p.defer_cap;
 	}
-	/* IPv6 rules beside the index: their lookups in the kernel's loop (1:
-	 * one IPv6 direction can hit, one line a frame; 2: both, the src line
-	 * beside the dst one), beside one live IPv4 direction or both (the
-	 * index never takes both directions with the u32 log: qt_log_fits) */
-	a.v6p = !(a.qt && a.v6d) ? 0u
-		: (a.t6.fmask & 3) == 3u ? 2u : (a.t6.fmask & 3) != 0 ? 1u : 0u;
-#ifdef XFG_DIAG
-	const char *v6e = getenv("XFG_V6P");   /* "off": every IPv6 frame deferred */
-	if (v6e && !strcmp(v6e, "off"))
-		a.v6p = 0;
-#endif
-	/* hit log (pipelined kernels): the hash-map counters without a direct
-	 * LDS counter, when the count kernel's histogram covers them; the wave
-	 * regions share the deferred lists' bound, the partition buffers hold
-	 * twice a uniform share (a fuller one spills to atomics) */
-	/* (with the quotient index the log holds QT slots only: its span) */
-	uint64_t total = a.qt ? (uint64_t)a.qt_n : (uint64_t)a.gbase[3] + XFG_PORT_MAP_ENTRIES;
-	uint64_t hist = ((total + 16 * XFG_LOG_PARTS - 1) / (16 * XFG_LOG_PARTS)) * 16;
-	/* (a range past one histogram: the count kernel takes it in passes; past
-	 * 65536 local indices the slices hold u32) */
-	const int pwide = hist > 65536;
-	const int logs = !log_off && !qt_nolog && hist <= (uint64_t)XFG_LOG_HIST_MAX * XFG_LOG_PASSES_MAX &&
-			 grid <= XFG_LOG_SLICES_MAX;
-	/* slice (partition, workgroup): twice a uniform share of the most the
-	 * workgroup's waves can log (a fuller one spills) */
-	/* (a workgroup's tiles are a fixed share whichever of its waves takes
-	 * them: the share, not the deferred lists' room) */
-	const uint64_t wg_nw = per_wg / 64, wg_all = grid * wg_nw;
-	const uint64_t wg_max = wg_nw * (((a.n + 63) / 64 + wg_all - 1) / wg_all) * 64;
-	const uint64_t pcap = (2 * ((wg_max + XFG_LOG_PARTS - 1) / XFG_LOG_PARTS) + 64 + 7) & ~7ull;
-	/* the quotient-index kernel's logs of up to K launches side by side in
-	 * the partition buffers, counted by one count kernel (its fixed cost
-	 * -- a pass over every QT-order count -- paid once per K launches);
-	 * every other log is counted after its own launch */
-	uint64_t K = 1;
-	if (logs && a.qt) {
-		K = XFG_LOG_PEND_MAX;
-#ifdef XFG_DIAG
-		const char *lp = getenv("XFG_LOG_PEND");   /* launches per count kernel (1: round 4) */
-		if (lp && *lp)
-			K = strtoul(lp, NULL, 0) ? strtoul(lp, NULL, 0) : 1;
-#endif
-		while (K > 1 && K * grid > XFG_LOG_SLICES_MAX)
-			K--;
+	if (p.defer_sep) {
+		if ((err = scratch(d, (void **)&d->defer_n, &d->defer_n_bytes, p.bytes.defer_n)))
+			goto out;
+		a->defer_n = d->defer_n;
+		a->defer_nsrc = p.defer_nsrc;
+		a->defer_sep = 1;
+		a->defer_grid = p.defer_grid;
 	}
-	/* the count wave (since round 6): the quotient-index kernel's ninth wave
-	 * counts the previous launch's log while the others classify, so no
-	 * count kernel runs between launches -- two sets of slices used in
-	 * turn; for a 64-byte window, a u16 log in one histogram of at most
-	 * XFG_CW_HIST_MAX (C3's 1M rules: 8192), no IPv6 lookups in the loop,
-	 * and the kernel launchable with its histogram */
-	const int occ_c = (a.dcnt > 0) | (!a.port_tab && a.port_count ? 2 : 0);
-	/* (measured, profiles/r06_s2_session.log: C3 at 2^24 0.294 against
-	 * 0.299 ms a launch; at 2^26 no better -- there the count kernel's
-	 * cost is its proportional part, which the count wave pays inside the
-	 * launch: it runs below XFG_CW_MAX_PACKETS) */
-	/* (the LDS Ethernet table and the histogram do not fit beside each other) */
-	int cw = logs && a.qt && !pwide && hist <= XFG_CW_HIST_MAX && a.window <= 64 && !a.v6p && !a.ek &&
-		 2 * grid <= XFG_LOG_SLICES_MAX && d->occ[7][0][occ_c] > 0 && a.n < XFG_CW_MAX_PACKETS;
-#ifdef XFG_DIAG
-	const char *cwe = getenv("XFG_CW");   /* "off": the count kernel every XFG_LOG_PEND launches */
-	if (cwe && !strcmp(cwe, "off"))
-		cw = 0;
-#endif
-	if (cw)
-		K = 2;
-	/* (the QT kernel's waves taking their workgroup's tiles as they go,
-	 * C3 on one box: 2^26 1.059-1.061 against 1.089-1.092 ms, 2^24
-	 * 0.294-0.296 against 0.304-0.306, 2^21 equal; C4 at 2^21 1.5 % slower
-	 * -- profiles/r06_s13_session.log) */
-	uint64_t dyn_min = XFG_QT_DYN_MIN;
-#ifdef XFG_DIAG
-	const char *dme = getenv("XFG_QT_DYN_MIN");   /* packets from which they do */
-	if (dme && *dme)
-		dyn_min = strtoull(dme, NULL, 0);
-#endif
-	a.qt_dyn = a.qt && a.n >= dyn_min;
 	/* logs pending from earlier launches: counted first unless this one
 	 * appends to them -- or, in the count wave's mode, counts them (the
 	 * same shape, the same counts) */
-	const int append = logs && K > 1 && d->log_pend && d->log_grid == grid &&
-			   d->log_args.pcap == pcap && d->log_args.pslices == K * grid &&
-			   d->log_args.log_span == hist && d->log_args.pwide == (uint32_t)pwide &&
-			   d->log_args.qt_hits == a.qt_hits && d->log_args.qt_n == a.qt_n &&
-			   d->log_cw == (uint32_t)cw;
+	const int append = p.logs && p.K > 1 && d->log_pend && d->log_grid == grid &&
+			   d->log_args.pcap == p.pcap && d->log_args.pslices == p.K * grid &&
+			   d->log_args.log_span == p.log_span && d->log_args.pwide == p.pwide &&
+			   d->log_args.qt_hits == a->qt_hits && d->log_args.qt_n == a->qt_n &&
+			   d->log_cw == (uint32_t)p.cw;
 	if (d->log_pend && !append && (err = log_flush_locked(d)))
 		goto out;
-	if (logs) {
-		/* (the quotient-index kernel combines its log in LDS and writes
-		 * the partition buffers itself: no per-wave regions) */
-		if ((!a.qt && (err = scratch(d, (void **)&d->tlog, &d->tlog_bytes,
-					     grid * (per_wg / 64) * (uint64_t)a.defer_cap * 4))) ||
-		    (err = scratch(d, (void **)&d->pbuf, &d->pbuf_bytes,
-				   ((uint64_t)XFG_LOG_PARTS * K * grid * pcap + 1024) * (pwide ? 4 : 2))) ||   /* (+ the count kernel's overread) */
-		    (err = scratch(d, (void **)&d->pfill, &d->pfill_bytes,
-				   (uint64_t)XFG_LOG_PARTS * K * grid * 4)))
+	if (p.logs) {
+		if ((err = scratch(d, (void **)&d->tlog, &d->tlog_bytes, p.bytes.tlog)) ||
+		    (err = scratch(d, (void **)&d->pbuf, &d->pbuf_bytes, p.bytes.pbuf)) ||
+		    (err = scratch(d, (void **)&d->pfill, &d->pfill_bytes, p.bytes.pfill)))
 			goto out;
-		a.tlog = a.qt ? NULL : d->tlog;
-		a.pbuf = d->pbuf;
-		a.pfill = d->pfill;
-		a.pcap = (uint32_t)pcap;
-		a.pslices = (uint32_t)(K * grid);
-		a.pslice0 = 0;
-		a.pcount = (uint32_t)grid;
-		a.log_hist = (uint32_t)(hist < XFG_LOG_HIST_MAX ? hist : XFG_LOG_HIST_MAX);
-		a.log_span = (uint32_t)hist;
-		a.pwide = (uint32_t)pwide;
+		a->tlog = p.bytes.tlog ? d->tlog : NULL;
+		a->pbuf = d->pbuf;
+		a->pfill = d->pfill;
+		a->pcap = p.pcap;
+		a->pslices = p.K * (uint32_t)grid;
+		a->pslice0 = 0;
+		a->pcount = (uint32_t)grid;
+		a->log_hist = p.log_hist;
+		a->log_span = p.log_span;
+		a->pwide = p.pwide;
 	}
-	if (a.qt && !a.pbuf && !qt_nolog) {   /* (decided above: cannot happen) */
-		err = -EIO;
+	if ((err = stream_enter(d, user)))
 		goto out;
-	}
-	if (user && user != (void *)d->stream) {
-		if ((err = hip_err(hipEventRecord(d->ev_user, (hipStream_t)user))) ||
-		    (err = hip_err(hipStreamWaitEvent(d->stream, d->ev_user, 0))))
-			goto out;
-	}
-	if (a.qt_hits && iters > 0)
+	if (a->qt_hits && iters > 0)
 		d->qt_pending = 1;
 	/* classify, then its hit log's count kernel, on the device stream (a
 	 * count kernel on a second stream, overlapped with the next classify,
 	 * shares the CUs and slowed the classify more than it hid:
 	 * profiles/archive/r04_s11_count_overlap.log) */
-	uint64_t fold_at = 0xffffffffull;   /* (a 32-bit QT-order count's room) */
-#ifdef XFG_DIAG
-	const char *fa = getenv("XFG_QT_FOLD_AT");   /* tests: fold after this many packets */
-	if (fa && strtoull(fa, NULL, 0))
-		fold_at = strtoull(fa, NULL, 0);
-#endif
+	/* (a fold before a 32-bit QT-order count could run out of room) */
+	const uint64_t fold_at = in->knobs && in->knobs->qt_fold_at ? in->knobs->qt_fold_at : 0xffffffffull;
 	for (int i = 0; i < iters && !err; i++) {
-		if (a.qt_hits) {
-			if (d->qt_pk + a.n > fold_at && (err = qt_fold_queued(d)))
+		if (a->qt_hits) {
+			if (d->qt_pk + a->n > fold_at && (err = qt_fold_queued(d)))
 				break;
-			d->qt_pk += a.n;
+			d->qt_pk += a->n;
 		}
-		a.cw_n = 0;
-		a.pfirst = 0;
-		if (a.pbuf && cw) {
+		a->cw_n = 0;
+		a->pfirst = 0;
+		if (a->pbuf && p.cw) {
 			/* the pending launch's set, counted by this launch's count
 			 * wave (or, with none pending, none); this launch's log
 			 * into the other set */
 			if (d->log_pend) {
-				a.cw_n = (uint32_t)grid;
-				a.cw_s0 = d->log_first;
+				a->cw_n = (uint32_t)grid;
+				a->cw_s0 = d->log_first;
 			}
-			a.pslice0 = d->log_pend && !d->log_first ? (uint32_t)grid : 0u;
-		} else if (a.pbuf && K > 1) {
-			a.pslice0 = d->log_pend * (uint32_t)grid;
+			a->pslice0 = d->log_pend && !d->log_first ? (uint32_t)grid : 0u;
+		} else if (a->pbuf && p.K > 1) {
+			a->pslice0 = d->log_pend * (uint32_t)grid;
 		}
-		err = xfg_launch_classify(ctx->prog_features, &a, (unsigned)grid, d->stream);
-		if (!err && a.pbuf && cw) {
-			d->log_args = a;
+		err = xfg_launch_classify(ctx->prog_features, a, (unsigned)grid, d->stream);
+		if (!err && a->pbuf && p.cw) {
+			d->log_args = *a;
 			d->log_grid = (uint32_t)grid;
 			d->log_pend = 1;
-			d->log_first = a.pslice0;
+			d->log_first = a->pslice0;
 			d->log_cw = 1;
-		} else if (!err && a.pbuf && K > 1) {
+		} else if (!err && a->pbuf && p.K > 1) {
 			if (!d->log_pend)
 				d->log_first = 0;
-			d->log_args = a;
+			d->log_args = *a;
 			d->log_grid = (uint32_t)grid;
 			d->log_cw = 0;
-			if (++d->log_pend == K)
+			if (++d->log_pend == p.K)
 				err = log_flush_locked(d);
 		} else if (!err) {
-			err = xfg_launch_log_count(&a, d->stream);
+			err = xfg_launch_log_count(a, d->stream);
 		}
 	}
 	if (!err)
-		d->last_kind = kind;
-	if (!err && user && user != (void *)d->stream) {
-		if (!(err = hip_err(hipEventRecord(d->ev_done, d->stream))))
-			err = hip_err(hipStreamWaitEvent((hipStream_t)user, d->ev_done, 0));
-	}
+		d->last_kind = p.kind;
+	if (!err)
+		err = stream_leave(d, user);
 out:
 	pthread_mutex_unlock(&d->lock);
 	return err;
@@ -2145,27 +1844,6 @@ static int check_batch(xfg_ctx *ctx, int dev, const struct xfg_batch *b, const v
 	return 0;
 }
 
-int xfg_classify(xfg_ctx *ctx, int dev, const struct xfg_batch *b, uint8_t *verdicts,
-		 void *stream)
-{
-	int err = check_batch(ctx, dev, b, verdicts);
-	if (err)
-		return err;
-	if (!b->count)
-		return 0;
-	struct xfg_dev *d = &ctx->dev[dev];
-	struct xfg_kargs a;
-	pthread_mutex_lock(&ctx->lock);
-	ctx->reduced = 0;
-	err = fill_kargs(ctx, d, b, verdicts, &a);
-	pthread_mutex_unlock(&ctx->lock);
-	if (!err)
-		err = hip_err(hipSetDevice(d->ordinal));
-	if (!err)
-		err = launch_batch(ctx, d, &a, stream, 1);
-	return err;
-}
-
 /* argument checks of the descriptor entry points; 1: an empty batch */
 static int check_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db, const void *verdicts)
 {
@@ -2182,15 +1860,50 @@ static int check_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db, c
 	return 0;
 }
 
-static int descs_kargs(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_desc_batch *db,
-		       uint8_t *verdicts, struct xfg_kargs *a)
+/* The four entry points' body, their arguments checked: @iters launches of
+ * @b, or of the descriptor batch @db; with @avg_ms between two events on
+ * the device's stream, the logs still pending counted inside the timed
+ * region (the iterations' work is complete when ev1 fires). */
+static int classify(xfg_ctx *ctx, int dev, const struct xfg_batch *b, const struct xfg_desc_batch *db,
+		    uint8_t *verdicts, void *stream, int iters, double *avg_ms)
 {
-	struct xfg_batch b = { db->umem, NULL, NULL, db->count, 0, 0 };
-	pthread_mutex_lock(&ctx->lock);
-	ctx->reduced = 0;
-	int err = fill_kargs_src(ctx, d, &b, db, verdicts, a);
-	pthread_mutex_unlock(&ctx->lock);
+	struct xfg_dev *d = &ctx->dev[dev];
+	struct xfg_batch umem;
+	struct launch l;
+	float ms = 0;
+	if (db) {
+		umem = (struct xfg_batch){ db->umem, NULL, NULL, db->count, 0, 0 };
+		b = &umem;
+	}
+	int err = snapshot(ctx, d, b, db, verdicts, 0, &l);
+	if (err)
+		return err;
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!avg_ms)
+		return launch_batch(ctx, d, &l, stream, iters);
+	HIPCHK(hipEventRecord(d->ev0, d->stream));
+	if ((err = launch_batch(ctx, d, &l, NULL, iters)))
+		goto fail;
+	pthread_mutex_lock(&d->lock);
+	err = log_flush_locked(d);
+	pthread_mutex_unlock(&d->lock);
+	if (err)
+		goto fail;
+	HIPCHK(hipEventRecord(d->ev1, d->stream));
+	HIPCHK(hipEventSynchronize(d->ev1));
+	HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
+	*avg_ms = ms / iters;
+fail:
 	return err;
+}
+
+int xfg_classify(xfg_ctx *ctx, int dev, const struct xfg_batch *b, uint8_t *verdicts,
+		 void *stream)
+{
+	int err = check_batch(ctx, dev, b, verdicts);
+	if (err || !b->count)
+		return err;
+	return classify(ctx, dev, b, NULL, verdicts, stream, 1, NULL);
 }
 
 int xfg_classify_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
@@ -2199,18 +1912,8 @@ int xfg_classify_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
 	int err = check_descs(ctx, dev, db, verdicts);
 	if (err)
 		return err < 0 ? err : 0;
-	struct xfg_dev *d = &ctx->dev[dev];
-	struct xfg_kargs a;
-	if ((err = descs_kargs(ctx, d, db, verdicts, &a)))
-		return err;
-	err = hip_err(hipSetDevice(d->ordinal));
-	if (!err)
-		err = launch_batch(ctx, d, &a, stream, 1);
-	return err;
+	return classify(ctx, dev, NULL, db, verdicts, stream, 1, NULL);
 }
-
-static int timed_launches(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_kargs *a, int iters,
-			  double *avg_ms);
 
 int xfg_classify_descs_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
 			     uint8_t *verdicts, int iters, double *avg_ms)
@@ -2220,11 +1923,7 @@ int xfg_classify_descs_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch 
 		return err;
 	if (iters < 1 || !avg_ms || err)   /* (an empty batch has no time) */
 		return -EINVAL;
-	struct xfg_dev *d = &ctx->dev[dev];
-	struct xfg_kargs a;
-	if ((err = descs_kargs(ctx, d, db, verdicts, &a)))
-		return err;
-	return timed_launches(ctx, d, &a, iters, avg_ms);
+	return classify(ctx, dev, NULL, db, verdicts, NULL, iters, avg_ms);
 }
 
 int xfg_classify_timed(xfg_ctx *ctx, int dev, const struct xfg_batch *b, uint8_t *verdicts,
@@ -2235,42 +1934,7 @@ int xfg_classify_timed(xfg_ctx *ctx, int dev, const struct xfg_batch *b, uint8_t
 		return err;
 	if (iters < 1 || !avg_ms)
 		return -EINVAL;
-	struct xfg_dev *d = &ctx->dev[dev];
-	struct xfg_kargs a;
-	pthread_mutex_lock(&ctx->lock);
-	ctx->reduced = 0;
-	err = fill_kargs(ctx, d, b, verdicts, &a);
-	pthread_mutex_unlock(&ctx->lock);
-	if (err)
-		return err;
-	return timed_launches(ctx, d, &a, iters, avg_ms);
-}
-
-/* @iters launches of one batch between two events on the device's stream
- * (xfg_classify_timed, xfg_classify_descs_timed) */
-static int timed_launches(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_kargs *a, int iters,
-			  double *avg_ms)
-{
-	int err;
-	float ms = 0;
-	HIPCHK(hipSetDevice(d->ordinal));
-	HIPCHK(hipEventRecord(d->ev0, d->stream));
-	if ((err = launch_batch(ctx, d, a, NULL, iters)))
-		goto fail;
-	/* (the logs still pending are counted inside the timed region: the
-	 * iterations' work is complete when ev1 fires) */
-	pthread_mutex_lock(&d->lock);
-	err = log_flush_locked(d);
-	pthread_mutex_unlock(&d->lock);
-	if (err)
-		goto fail;
-	HIPCHK(hipEventRecord(d->ev1, d->stream));
-	HIPCHK(hipEventSynchronize(d->ev1));
-	HIPCHK(hipEventElapsedTime(&ms, d->ev0, d->ev1));
-	*avg_ms = ms / iters;
-	return 0;
-fail:
-	return err;
+	return classify(ctx, dev, b, NULL, verdicts, NULL, iters, avg_ms);
 }
 
 /* Room for @words status words in the device's tile status buffer (d->lock
@@ -2315,17 +1979,12 @@ int xfg_compact(xfg_ctx *ctx, int dev, const uint8_t *verdicts, uint64_t n, uint
 		HIPCHK(hipMalloc((void **)&d->cticket, 4));
 	if ((err = cstatus_room(d, tiles)))
 		goto fail;
-	hipStream_t user = (hipStream_t)stream;
-	if (user && user != d->stream) {
-		HIPCHK(hipEventRecord(d->ev_user, user));
-		HIPCHK(hipStreamWaitEvent(d->stream, d->ev_user, 0));
-	}
+	if ((err = stream_enter(d, stream)))
+		goto fail;
 	err = xfg_launch_compact(verdicts, n, action, idx, (unsigned long long *)count,
 				 d->cstatus, d->cticket, (unsigned)d->ncu * 4, d->stream);
-	if (!err && user && user != d->stream) {
-		HIPCHK(hipEventRecord(d->ev_done, d->stream));
-		HIPCHK(hipStreamWaitEvent(user, d->ev_done, 0));
-	}
+	if (!err)
+		err = stream_leave(d, stream);
 fail:
 	pthread_mutex_unlock(&d->lock);
 	return err;
@@ -2385,16 +2044,12 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uin
 		.n = (uint32_t)e->count,
 		.swap_macs = !!(e->flags & XFG_EGRESS_SWAP_MACS),
 	};
-	if (user && user != d->stream) {
-		HIPCHK(hipEventRecord(d->ev_user, user));
-		HIPCHK(hipStreamWaitEvent(d->stream, d->ev_user, 0));
-	}
+	if ((err = stream_enter(d, stream)))
+		goto fail;
 	/* (four workgroups a CU: all of them resident) */
 	err = xfg_launch_egress(&a, (unsigned)d->ncu * 4, d->stream);
-	if (!err && user && user != d->stream) {
-		HIPCHK(hipEventRecord(d->ev_done, d->stream));
-		HIPCHK(hipStreamWaitEvent(user, d->ev_done, 0));
-	}
+	if (!err)
+		err = stream_leave(d, stream);
 fail:
 	pthread_mutex_unlock(&d->lock);
 	return err;
@@ -2437,16 +2092,12 @@ static int capture_launch(xfg_ctx *ctx, int dev, struct xfg_capture_kargs *a, ui
 	a->n = (uint32_t)count;
 	a->action_mask = c->action_mask;
 	a->snaplen = c->snaplen;
-	if (user && user != d->stream) {
-		HIPCHK(hipEventRecord(d->ev_user, user));
-		HIPCHK(hipStreamWaitEvent(d->stream, d->ev_user, 0));
-	}
+	if ((err = stream_enter(d, stream)))
+		goto fail;
 	/* (four workgroups a CU: all of them resident) */
 	err = xfg_launch_capture(a, (unsigned)d->ncu * 4, d->stream);
-	if (!err && user && user != d->stream) {
-		HIPCHK(hipEventRecord(d->ev_done, d->stream));
-		HIPCHK(hipStreamWaitEvent(user, d->ev_done, 0));
-	}
+	if (!err)
+		err = stream_leave(d, stream);
 fail:
 	pthread_mutex_unlock(&d->lock);
 	return err;
@@ -2687,21 +2338,16 @@ fail:
 static int host_launch(xfg_ctx *ctx, struct xfg_dev *d, const struct xfg_batch *sub,
 		       uint8_t *dv, int hwin, uint32_t *fb, uint32_t *fbc, hipStream_t st)
 {
-	struct xfg_kargs a;
-	pthread_mutex_lock(&ctx->lock);
-	ctx->reduced = 0;
-	int err = fill_kargs(ctx, d, sub, dv, &a);
-	pthread_mutex_unlock(&ctx->lock);
+	struct launch l;
+	int err = snapshot(ctx, d, sub, NULL, dv, hwin, &l);
 	if (err)
 		return err;
-	if (hwin) {   /* header windows: the general kernel, listing what leaves them */
-		a.pipe = 0;
-		a.hwin = 1;
-		a.fb = fb;
-		a.fb_cnt = fbc;
-		a.fb_cap = HOST_CH;
+	if (hwin) {   /* header windows (the general kernel): listing what leaves them */
+		l.a.fb = fb;
+		l.a.fb_cnt = fbc;
+		l.a.fb_cap = HOST_CH;
 	}
-	return launch_batch(ctx, d, &a, st, 1);
+	return launch_batch(ctx, d, &l, st, 1);
 }
 
 /* The packets of the chunk at `c` whose programs left their windows (count
