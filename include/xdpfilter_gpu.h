@@ -212,7 +212,9 @@ int xfg_classify(xfg_ctx *ctx, int dev, const struct xfg_batch *batch,
  * bytes long.  mask = ring entries - 1 (a power of two), or 0xffffffff for
  * a plain array.  Frame starts must be 16-byte aligned (default UMEM frame
  * sizes and headroom are) and readable up to the next 16-byte boundary past
- * their end.  Single-buffer descriptors only (XDP_PKT_CONTD clear).
+ * their end.  Every record is taken as a whole packet (XDP_PKT_CONTD is not
+ * looked at): the batches of a socket bound with XDP_USE_SG, whose packets may
+ * span several records, go through xfg_classify_descs_frags.
  */
 struct xfg_desc_batch {
 	const void *umem;
@@ -224,6 +226,77 @@ struct xfg_desc_batch {
 
 int xfg_classify_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
 		       uint8_t *verdicts, void *stream);
+
+/*
+ * Multi-buffer AF_XDP packets (a socket bound with XDP_USE_SG delivers a frame
+ * longer than its chunk, or an LRO/GRO aggregate, as several RX records):
+ * classify by the head record, one verdict byte per record.
+ *
+ * Packets, as l2fwd() and rx_drop() take them (lib/util/xdpsock.c:70,
+ * 1228-1257,1500-1548): a packet is a maximal run of consecutive records of
+ * @batch ending at the first one whose options & XFG_XDP_PKT_CONTD is 0
+ * (IS_EOP_DESC); other option bits are ignored.  Record 0 starts a packet: the
+ * caller released exactly counts[1] records after the previous batch, as
+ * l2fwd releases frags_done.
+ *
+ * An XDP program sees the first buffer only (ctx->data .. ctx->data_end is the
+ * head fragment), so a packet's verdict, rule hit and stats are those of the
+ * program run on its head record alone, with len the head's len: rx_bytes
+ * counts the head's bytes, not the packet's (headers/xdp/xdp_stats_kern.h:
+ * 44-45).  Continuation records are never parsed and bump no counter and no
+ * statistic.  A packet the batch ends in the middle of is not processed at
+ * all -- no verdict, no stats; the caller leaves its records on the ring for
+ * the next batch (lib/util/xdpsock.c:1539-1542).
+ *
+ * Out: counts[0] = complete packets, counts[1] = the records in them
+ * (l2fwd's frags_done: what to release, and the count of the egress call),
+ * counts[2] = the records of the trailing incomplete packet; counts[1] +
+ * counts[2] == count.  counts is HOST memory, valid when the call returns.
+ * verdicts (device, count bytes): every record of a complete packet gets its
+ * packet's verdict, so xfg_ring_egress (with XFG_EGRESS_MULTIBUF) and
+ * xfg_capture_descs keep their per-record interface; bytes at indices >=
+ * counts[1] are not written.  pkt_of (device, count x u32, or NULL): record
+ * i's packet index, the number of end-of-packet records before it, written
+ * for all count records; the value counts[0] marks the trailing incomplete
+ * packet.
+ *
+ * Three steps on the device: a head pass over the records (one kernel: the
+ * packet indices, the head records gathered into a plain descriptor array in
+ * library scratch, the counts); the counts read back to the host; the
+ * counts[0] heads classified as xfg_classify_descs classifies a plain array
+ * of that many records -- xfg_last_path and xfg_open_opts.descs_min_packets
+ * behave as for such a call -- and their verdicts spread over the records.
+ * The read-back is the call's one host synchronisation, after it has ordered
+ * itself behind @stream, and it is deliberate: the classify launch is planned
+ * on the host from the packet count (kernel, grid, the descs_min_packets
+ * threshold; xfg_plan.c), and the caller needs counts[1] on the host for
+ * xsk_ring_cons__release anyway.  (Classifying all count records with no-op
+ * entries for the continuations would run the program on things that are not
+ * packets and need the ABORTED statistic repaired afterwards.)  The classify
+ * and the spread are stream-ordered; the call returns without waiting for
+ * them, and @stream's later work runs after them.
+ *
+ * -EINVAL: what xfg_classify_descs refuses, fr == NULL, sz below the
+ * structure's size, pkt_of not 4-byte aligned, count >= 2^32.  -ENODEV on a
+ * host-only context.  count == 0: three zero counts, nothing launched.  No
+ * end-of-packet record in the batch: {0, 0, count}, nothing classified, no
+ * stats change, verdicts untouched.
+ *
+ * Not covered: xfg_capture_descs of multi-buffer packets (it keeps capturing
+ * record by record, each record's bytes under its packet's verdict),
+ * xfg_classify_xsk_host, and the CLI.
+ */
+#define XFG_XDP_PKT_CONTD (1u << 0)          /* headers/linux/if_xdp.h:123 */
+
+struct xfg_frags {
+	size_t sz;            /* sizeof(struct xfg_frags), for extension */
+	uint32_t *pkt_of;     /* device, count x u32, or NULL: record i's packet index */
+	uint64_t counts[3];   /* HOST, out: packets, records in them (l2fwd's frags_done),
+	                       * records of the trailing incomplete packet */
+};
+
+int xfg_classify_descs_frags(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
+			     struct xfg_frags *fr, uint8_t *verdicts, void *stream);
 
 /*
  * Host-resident batch (struct xfg_batch in host memory): classifies it on
@@ -336,9 +409,24 @@ int xfg_compact(xfg_ctx *ctx, int dev, const uint8_t *verdicts, uint64_t n, uint
  *
  * Stream-ordered on @stream (NULL: the library's stream of the device), as
  * xfg_compact is: after xfg_classify_descs on the same stream it needs no
- * host synchronisation.  Single-buffer descriptors only.
+ * host synchronisation.
+ *
+ * XFG_EGRESS_MULTIBUF: the batch holds multi-buffer packets classified by
+ * xfg_classify_descs_frags -- count = its counts[1], @verdicts its per-record
+ * verdicts.  A TX record's options is then the RX record's options &
+ * XFG_XDP_PKT_CONTD instead of 0 (tx_desc->options = eop ? 0 : XDP_PKT_CONTD,
+ * lib/util/xdpsock.c:1528), and XFG_EGRESS_SWAP_MACS touches head records
+ * only (lib/util/xdpsock.c:1521-1522): record 0, and record i iff record
+ * i - 1 has the bit clear.  All records of a packet carry one verdict, so the
+ * order-preserving partition keeps a PASS packet's records adjacent and in
+ * order on the TX ring and hands every chunk of any other packet to the fill
+ * ring (rx_drop, lib/util/xdpsock.c:1248); counts stay per record, as
+ * l2fwd's tx_frags is.  Without the flag every record is a packet of its own
+ * (single-buffer descriptors, options 0 in the TX records).  The flag is bit
+ * 2: bit 1 stays an unknown flag, refused as before.
  */
 #define XFG_EGRESS_SWAP_MACS (1u << 0)
+#define XFG_EGRESS_MULTIBUF  (1u << 2)
 
 struct xfg_egress {
 	size_t sz;              /* sizeof(struct xfg_egress), for extension */
@@ -398,7 +486,8 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e,
  * Stream-ordered on @stream (NULL: the library's stream of the device), as
  * xfg_compact and xfg_ring_egress are: after a classify call on the same
  * stream it needs no host synchronisation.  The call changes no map, counter
- * or statistic.  Single-buffer descriptors only.
+ * or statistic.  Single-buffer descriptors only: a multi-buffer packet's
+ * records (xfg_classify_descs_frags) are captured record by record.
  */
 struct xfg_capture {
 	size_t sz;              /* sizeof(struct xfg_capture), for extension */
@@ -444,6 +533,12 @@ int xfg_classify_timed(xfg_ctx *ctx, int dev, const struct xfg_batch *batch,
  * region.  -EINVAL for an empty batch. */
 int xfg_classify_descs_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
 			     uint8_t *verdicts, int iters, double *avg_ms);
+/* One xfg_classify_descs_frags call on the library's stream with each of its
+ * three steps between two events and waited for: ms[0] the head pass, ms[1]
+ * the classify of the heads, ms[2] the spread (0 for a step that did not
+ * run). */
+int xfg_classify_descs_frags_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
+				   struct xfg_frags *fr, uint8_t *verdicts, double ms[3]);
 
 /* Streaming-read probe: average duration of a kernel that reads @bytes of
  * device memory at @src with 16-byte non-temporal loads (the achievable HBM

@@ -31,6 +31,14 @@
       (xfg_capture_descs, snaplen 0), beside xfg_compact; the same ring with
       1514-byte frames at snaplen 96, one in ten selected; one tile of
       packets for the fixed cost of a call -- timed as c3f's legs are
+  c3m  c3d's UMEM and rules with every C3 frame the head of a 3-record packet
+      (XDP_PKT_CONTD, a socket bound with XDP_USE_SG): two continuation chunks a
+      packet, each holding a frame that hits a rule -- 2^22 packets, 3 * 2^22
+      records.  xfg_classify_descs_frags: its head pass, the classify of the
+      heads and the spread (events around each, xfg_classify_descs_frags_timed),
+      the whole call (wall clock to its return, and to the stream's end), the
+      egress with XFG_EGRESS_MULTIBUF timed as c3f's legs are, and c3d
+      (xfg_classify_descs_timed) on the same heads for comparison
 
   c1 xdpfilt_alw_eth, the 8 MAC rules 02:00:00:00:00:0{1..8} (4 dst, 4
       src), 64 B Ethernet/IPv4/UDP frames, 25% carrying a ruled MAC (SURVEY.md
@@ -117,9 +125,11 @@ def run_c1(args):
 C3D_CHUNK, C3D_HEADROOM = 2048, 256
 
 
-def c3d_workload(args, tag):
+def c3d_workload(args, tag, umem_chunks=1):
     """C3's frames in a device UMEM behind an RX ring that wraps, the rules
-    loaded (c3d, c3f).  Returns a namespace of what the legs use."""
+    loaded (c3d, c3f).  Returns a namespace of what the legs use.
+    umem_chunks: the UMEM's chunks per frame (c3m's continuation chunks lie
+    past the frames')."""
     import types
     import numpy as np
     import xftools as X
@@ -143,7 +153,7 @@ def c3d_workload(args, tag):
     perm = rng.permutation(n)
     inv = np.empty(n, np.int64)
     inv[perm] = np.arange(n)
-    d_umem = f.alloc(n * C3D_CHUNK)
+    d_umem = f.alloc(umem_chunks * n * C3D_CHUNK)
     frames = data.reshape(n, stride)
     piece = 1 << 17
     buf = np.zeros((piece, C3D_CHUNK), np.uint8)
@@ -164,7 +174,7 @@ def c3d_workload(args, tag):
     setup_s = time.time() - t0
     print(f"[{tag}] set up {setup_s:.1f}s", file=sys.stderr, flush=True)
     return types.SimpleNamespace(f=f, n=n, n4=n4, nports=nports, stride=stride, data=data, lens=lens,
-                                 d_umem=d_umem, d_descs=d_descs, d_verd=d_verd, entries=entries,
+                                 perm=perm, d_umem=d_umem, d_descs=d_descs, d_verd=d_verd, entries=entries,
                                  first=first, setup_s=setup_s)
 
 
@@ -370,6 +380,138 @@ def run_c3c(args):
     print(json.dumps(line), flush=True)
 
 
+def run_c3m(args):
+    """c3d's frames as the heads of 3-record packets (see the module text)."""
+    import numpy as np
+    import torch
+    import xfgpu as G
+    w = c3d_workload(args, "c3m", umem_chunks=3)
+    f, n, stride = w.f, w.n, w.stride
+    t0 = time.time()
+    # c3d on the heads alone, and their verdicts: the frames that hit a rule
+    a = (w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr)
+    f.classify_descs_timed(*a, 2, first=w.first, mask=w.entries - 1)
+    runs = max(1, args.runs)
+    c3d_ms = [f.classify_descs_timed(*a, args.iters, first=w.first, mask=w.entries - 1)
+              for _ in range(runs)]
+    c3d_path = f.last_path()
+    hv = w.d_verd.download(np.zeros(n, np.uint8))
+    hit = np.flatnonzero(hv == 2)[:4096]          # (deny program: a hit passes)
+    assert len(hit) >= 16, "no frames that hit a rule"
+    frames = w.data.reshape(n, stride)
+    # continuation chunk c (of 2n, past the heads' chunks) holds a hit frame
+    rng = np.random.default_rng(14)
+    cperm = rng.permutation(2 * n)                # continuation k of packet i: chunk n + cperm[2i + k]
+    which = hit[rng.integers(0, len(hit), 2 * n)]
+    cinv = np.empty(2 * n, np.int64)
+    cinv[cperm] = np.arange(2 * n)
+    piece = 1 << 17
+    buf = np.zeros((piece, C3D_CHUNK), np.uint8)
+    for c0 in range(0, 2 * n, piece):
+        c1 = min(2 * n, c0 + piece)
+        buf[:c1 - c0, C3D_HEADROOM:C3D_HEADROOM + stride] = frames[which[cinv[c0:c1]]]
+        G._check(G.lib.xfg_memcpy_h2d(f.ctx, 0, w.d_umem.ptr + (n + c0) * C3D_CHUNK, buf.ctypes.data,
+                                      (c1 - c0) * C3D_CHUNK), "memcpy_h2d")
+    nrec = 3 * n
+    entries = 1 << (nrec - 1).bit_length()
+    first = entries - 777
+    rec = np.zeros((n, 3, 2), np.uint64)
+    rec[:, 0, 0] = w.perm.astype(np.uint64) * np.uint64(C3D_CHUNK) + np.uint64(C3D_HEADROOM)
+    rec[:, 0, 1] = w.lens.astype(np.uint64) | np.uint64(G.XDP_PKT_CONTD << 32)
+    for k in (1, 2):
+        rec[:, k, 0] = (n + cperm[k - 1::2]).astype(np.uint64) * np.uint64(C3D_CHUNK) + np.uint64(C3D_HEADROOM)
+        rec[:, k, 1] = w.lens[which[cinv[cperm[k - 1::2]]]].astype(np.uint64) | \
+            np.uint64((G.XDP_PKT_CONTD if k == 1 else 0) << 32)
+    descs = np.zeros((entries, 2), np.uint64)
+    descs[(first + np.arange(nrec)) & (entries - 1)] = rec.reshape(nrec, 2)
+    d_descs, d_verd, d_pkt = f.alloc(descs.nbytes), f.alloc(nrec), f.alloc(4 * nrec)
+    d_descs.upload(descs)
+    del descs, rec, buf
+    print(f"[c3m] continuations set up {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
+    fa = (w.d_umem.ptr, d_descs.ptr, nrec, d_verd.ptr)
+    fk = dict(pkt_of_ptr=d_pkt.ptr, first=first, mask=entries - 1)
+    f.stats_reset()
+    counts = f.classify_descs_frags(*fa, **fk)
+    f.sync()
+    assert counts == (n, nrec, 0), counts
+    # the heads' verdicts on every record of their packets, and only the heads counted
+    v = d_verd.download(np.zeros(nrec, np.uint8)).reshape(n, 3)
+    assert np.array_equal(v, np.repeat(hv[:, None], 3, axis=1)), "verdicts differ from c3d's"
+    st = f.stats()
+    assert int(st[:, 0].sum()) == n, st
+    frags_path = f.last_path()
+    steps = {"head_pass": [], "classify_heads": [], "spread": []}
+    wall_return, wall_done = [], []
+    for _ in range(runs):
+        for _ in range(max(1, args.iters // 2)):
+            _, ms = f.classify_descs_frags_timed(*fa, **fk)
+            for k, m in zip(steps, ms):
+                steps[k].append(m)
+        f.sync()
+        t1 = time.perf_counter()
+        for _ in range(args.iters):
+            f.classify_descs_frags(*fa, **fk)
+        t2 = time.perf_counter()
+        f.sync()
+        t3 = time.perf_counter()
+        wall_return.append((t2 - t1) / args.iters * 1e3)
+        wall_done.append((t3 - t1) / args.iters * 1e3)
+    # the egress of the 3n records, as c3f times its legs
+    npass = int(np.count_nonzero(v == 2))
+    te = 1 << (nrec - 1).bit_length()
+    d_tx, d_fill, d_c = f.alloc(16 * te), f.alloc(8 * te), f.alloc(16)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def egress(flags):
+        f.ring_egress(d_descs.ptr, nrec, d_verd.ptr, d_c.ptr, tx_ptr=d_tx.ptr, fill_ptr=d_fill.ptr,
+                      rx_first=first, rx_mask=entries - 1, tx_first=te - 777, tx_mask=te - 1,
+                      fill_first=te - 555, fill_mask=te - 1, umem_ptr=w.d_umem.ptr, flags=flags,
+                      stream=sp)
+
+    legs = {"egress": lambda: egress(0),
+            "egress_multibuf": lambda: egress(G.EGRESS_MULTIBUF),
+            "egress_multibuf_swap_macs": lambda: egress(G.EGRESS_MULTIBUF | G.EGRESS_SWAP_MACS)}
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            call()
+        e0.record(stream)
+        for _ in range(args.iters):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    ems = {k: [] for k in legs}
+    for _ in range(runs):
+        for k, call in legs.items():
+            ems[k].append(timed(call))
+    ec = d_c.download(np.zeros(2, np.uint64)).tolist()
+    assert ec == [npass, nrec - npass], ec
+    best = {k: min(x) for k, x in steps.items()}
+    line = {"config": "c3m", "program": f.prog_name, "packets": n, "records": nrec,
+            "ring_entries": entries, "iters": args.iters,
+            "kernel_path_heads": frags_path,
+            "frags_ms": {k: round(m, 4) for k, m in best.items()},
+            "frags_steps_sum_ms": round(sum(best.values()), 4),
+            "frags_call_wall_ms": {"to_return": [round(m, 4) for m in wall_return],
+                                   "to_stream_end": [round(m, 4) for m in wall_done]},
+            "passes_over_classify": round((best["head_pass"] + best["spread"]) / best["classify_heads"], 3),
+            "c3d_same_heads": {"kernel_path": c3d_path, "kernel_ms": [round(m, 4) for m in c3d_ms],
+                               "Mpps": [round(n / (m * 1e-3) / 1e6, 1) for m in c3d_ms]},
+            "Mpps_whole_call": round(n / (min(wall_done) * 1e-3) / 1e6, 1),
+            "bytes": {"head_pass": 16 * nrec + 4 * nrec + 16 * n, "spread": 4 * nrec + nrec + n},
+            "pass_records": npass, "setup_s": round(w.setup_s + time.time() - t0, 1)}
+    for k in ("head_pass", "spread"):
+        line["GBps_" + k] = round(line["bytes"][k] / (best[k] * 1e-3) / 1e9, 1)
+    for k in legs:
+        line[k] = {"ms": [round(m, 4) for m in ems[k]]}
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
 def run(name, args):
     import numpy as np
     import xftools as X
@@ -382,6 +524,8 @@ def run(name, args):
         return run_c3d(args)
     if name == "c3f":
         return run_c3f(args)
+    if name == "c3m":
+        return run_c3m(args)
     kind = {"c2": 2, "c3": 3, "c4": 4, "c5": 5, "c3sd": 3, "c3e": 3}[name]
     n = 1 << (args.log2_packets or {"c2": 24, "c3": 24, "c4": 23, "c5": 23, "c3sd": 24, "c3e": 24}[name])
     stride = 64 if kind in (2, 3) else 1536

@@ -43,6 +43,9 @@ int xfg_launch_compact(const uint8_t *verdicts, uint64_t n, uint32_t action, uin
 uint64_t xfg_compact_tiles(uint64_t n);
 int xfg_launch_egress(const struct xfg_egress_kargs *a, unsigned grid, void *stream);
 int xfg_launch_capture(const struct xfg_capture_kargs *a, unsigned grid, void *stream);
+int xfg_launch_frags_heads(const struct xfg_frags_kargs *a, unsigned grid, void *stream);
+int xfg_launch_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *verdicts,
+			    uint32_t done, unsigned grid, void *stream);
 int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 		       unsigned long long *hits, uint32_t n, void *stream);
 
@@ -144,6 +147,14 @@ struct xfg_dev {
 	unsigned long long *cstatus;    /* verdict compaction, egress, capture: tile status words */
 	uint64_t cstatus_cap;
 	uint32_t *cticket;
+	/* multi-buffer descriptor batches (xfg_classify_descs_frags), one call
+	 * at a time under frags_lock: the head records, the per-packet verdicts
+	 * and, where the caller wants none, the records' packet indices */
+	pthread_mutex_t frags_lock;
+	void *fr_heads;
+	uint8_t *fr_pv;
+	uint32_t *fr_pkt;
+	uint64_t fr_heads_bytes, fr_pv_bytes, fr_pkt_bytes;
 	hipEvent_t ev_user, ev_done;    /* ordering against a caller's stream */
 };
 
@@ -395,6 +406,7 @@ static void dev_free(struct xfg_dev *d)
 	if (d->lock_ok) {
 		pthread_mutex_destroy(&d->lock);
 		pthread_mutex_destroy(&d->host_lock);
+		pthread_mutex_destroy(&d->frags_lock);
 		d->lock_ok = 0;
 	}
 	if (hipSetDevice(d->ordinal) != hipSuccess)
@@ -450,6 +462,9 @@ static void dev_free(struct xfg_dev *d)
 	hipFree(d->rec);
 	hipFree(d->pfill);
 	hipFree(d->cticket);
+	hipFree(d->fr_heads);
+	hipFree(d->fr_pv);
+	hipFree(d->fr_pkt);
 	if (d->ev_user)
 		hipEventDestroy(d->ev_user);
 	if (d->ev_done)
@@ -469,6 +484,7 @@ static int dev_init(xfg_ctx *ctx, struct xfg_dev *d)
 
 	pthread_mutex_init(&d->lock, NULL);
 	pthread_mutex_init(&d->host_lock, NULL);
+	pthread_mutex_init(&d->frags_lock, NULL);
 	d->lock_ok = 1;
 	HIPCHK(hipSetDevice(d->ordinal));
 	HIPCHK(hipGetDeviceProperties(&prop, d->ordinal));
@@ -2004,7 +2020,7 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uin
 {
 	int err = 0;
 	if (!ctx || !e || e->sz < sizeof(*e) || !e->counts || ((uintptr_t)e->counts & 7) ||
-	    (e->flags & ~XFG_EGRESS_SWAP_MACS) || e->count > 0xffffffffull ||
+	    (e->flags & ~(XFG_EGRESS_SWAP_MACS | XFG_EGRESS_MULTIBUF)) || e->count > 0xffffffffull ||
 	    (!e->tx_descs && !e->fill_addrs))
 		return -EINVAL;
 	if (!mask_ok(e->rx_mask) || !mask_ok(e->tx_mask) || !mask_ok(e->fill_mask))
@@ -2043,6 +2059,7 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uin
 		.fill_first = e->fill_first, .fill_mask = e->fill_mask,
 		.n = (uint32_t)e->count,
 		.swap_macs = !!(e->flags & XFG_EGRESS_SWAP_MACS),
+		.multibuf = !!(e->flags & XFG_EGRESS_MULTIBUF),
 	};
 	if ((err = stream_enter(d, stream)))
 		goto fail;
@@ -2053,6 +2070,118 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uin
 fail:
 	pthread_mutex_unlock(&d->lock);
 	return err;
+}
+
+/* Multi-buffer descriptor batches (include/xdpfilter_gpu.h): the head pass
+ * over the records, its counts read back (the call's one host
+ * synchronisation: the classify launch is planned from the packet count), the
+ * packets' head records classified as a plain descriptor array through
+ * classify(), and their verdicts spread over the records.  All of it on the
+ * device's own stream, after @stream's earlier work and before its later;
+ * frags_lock keeps a second caller off the head and verdict scratch between
+ * the steps (d->lock itself is released for classify(), which takes it).
+ * @ms (the timed entry point): the three steps' durations, each between two
+ * events and waited for. */
+static int frags_run(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db, struct xfg_frags *fr,
+		     uint8_t *verdicts, void *stream, double *ms)
+{
+	if (!db || !fr || fr->sz < sizeof(*fr) || ((uintptr_t)fr->pkt_of & 3) ||
+	    db->count > 0xffffffffull)
+		return -EINVAL;
+	int err = check_descs(ctx, dev, db, verdicts);
+	if (err < 0)
+		return err;
+	fr->counts[0] = fr->counts[1] = fr->counts[2] = 0;
+	if (ms)
+		ms[0] = ms[1] = ms[2] = 0;
+	if (err)   /* an empty batch */
+		return 0;
+	struct xfg_dev *d = &ctx->dev[dev];
+	const uint64_t n = db->count;
+	unsigned long long got[2] = { 0, 0 };
+	float t = 0;
+	int entered = 0;
+	pthread_mutex_lock(&d->frags_lock);
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if ((err = cstatus_room(d, XFG_FRAGS_STATE_WORDS(n))) ||
+	    (err = scratch(d, &d->fr_heads, &d->fr_heads_bytes, n * 16)) ||
+	    (err = scratch(d, (void **)&d->fr_pv, &d->fr_pv_bytes, n)) ||
+	    (!fr->pkt_of && (err = scratch(d, (void **)&d->fr_pkt, &d->fr_pkt_bytes, n * 4))))
+		goto fail;
+	uint32_t *pkt_of = fr->pkt_of ? fr->pkt_of : d->fr_pkt;
+	struct xfg_frags_kargs a = {
+		.rx = db->descs, .pkt_of = pkt_of, .heads = d->fr_heads, .state = d->cstatus,
+		.first = db->first, .mask = db->mask, .n = (uint32_t)n,
+	};
+	if ((err = stream_enter(d, stream)))
+		goto fail;
+	entered = 1;
+	if (ms)
+		HIPCHK(hipEventRecord(d->ev0, d->stream));
+	/* (four workgroups a CU: all of them resident) */
+	if ((err = xfg_launch_frags_heads(&a, (unsigned)d->ncu * 4, d->stream)))
+		goto fail;
+	if (ms)
+		HIPCHK(hipEventRecord(d->ev1, d->stream));
+	HIPCHK(hipMemcpyAsync(got, d->cstatus + 2, sizeof(got), hipMemcpyDeviceToHost, d->stream));
+	HIPCHK(hipStreamSynchronize(d->stream));
+	if (ms) {
+		HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
+		ms[0] = t;
+	}
+	if (got[0] > n || got[1] > n || (got[0] != 0) != (got[1] != 0)) {
+		err = -EIO;
+		goto fail;
+	}
+	fr->counts[0] = got[0];
+	fr->counts[1] = got[1];
+	fr->counts[2] = n - got[1];
+	pthread_mutex_unlock(&d->lock);
+	if (got[0]) {
+		const struct xfg_desc_batch hb = { db->umem, d->fr_heads, 0, 0xffffffffu, got[0] };
+		if ((err = classify(ctx, dev, NULL, &hb, d->fr_pv, NULL, 1, ms ? &ms[1] : NULL)))
+			goto leave;
+	}
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (got[1]) {
+		if (ms)
+			HIPCHK(hipEventRecord(d->ev0, d->stream));
+		if ((err = xfg_launch_frags_spread(d->fr_pv, pkt_of, verdicts, (uint32_t)got[1],
+						   (unsigned)d->ncu * 8, d->stream)))
+			goto fail;
+		if (ms) {
+			HIPCHK(hipEventRecord(d->ev1, d->stream));
+			HIPCHK(hipEventSynchronize(d->ev1));
+			HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
+			ms[2] = t;
+		}
+	}
+fail:
+	/* (also after an error: the caller's stream behind what was queued) */
+	if (entered) {
+		const int e2 = stream_leave(d, stream);
+		err = err ? err : e2;
+	}
+	pthread_mutex_unlock(&d->lock);
+leave:
+	pthread_mutex_unlock(&d->frags_lock);
+	return err;
+}
+
+int xfg_classify_descs_frags(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+			     struct xfg_frags *fr, uint8_t *verdicts, void *stream)
+{
+	return frags_run(ctx, dev, db, fr, verdicts, stream, NULL);
+}
+
+int xfg_classify_descs_frags_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+				   struct xfg_frags *fr, uint8_t *verdicts, double ms[3])
+{
+	if (!ms)
+		return -EINVAL;
+	return frags_run(ctx, dev, db, fr, verdicts, NULL, ms);
 }
 
 /* Capture by verdict (include/xdpfilter_gpu.h): both entry points fill the

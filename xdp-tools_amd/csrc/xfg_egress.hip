@@ -26,6 +26,13 @@
 // load and store of the frame's first 16 bytes (frame starts are 16-byte
 // aligned), bytes 12..15 rewritten with their own values.  It depends on the
 // verdict alone, so it is issued before the look-back's wait.
+//
+// XFG_EGRESS_MULTIBUF (multi-buffer packets, every record of one carrying its
+// packet's verdict: xfg_classify_descs_frags()): a TX record keeps the RX
+// record's XDP_PKT_CONTD (tx_desc->options = eop ? 0 : XDP_PKT_CONTD,
+// lib/util/xdpsock.c:1528) and the swap touches a packet's first record only
+// (lib/util/xdpsock.c:1521-1522).  The partition itself is the same: it keeps
+// the order, so a PASS packet's records stay adjacent on the TX ring.
 
 namespace {
 constexpr int EG_LANES = 256;
@@ -38,6 +45,8 @@ typedef __attribute__((address_space(1))) u32x4_a8 gdesc_w;
 typedef __attribute__((address_space(1))) u32x4 gu32x4_w;
 typedef __attribute__((address_space(1))) uint64_t gu64_w;
 typedef const __attribute__((address_space(1))) uint8_t gu8;
+typedef const __attribute__((address_space(1))) uint32_t eg_gu32;
+constexpr uint32_t EG_CONTD = 1u;   // XDP_PKT_CONTD, headers/linux/if_xdp.h:123
 }  // namespace
 
 __global__ __launch_bounds__(EG_LANES) void xfg_egress_kernel(const xfg_egress_kargs a)
@@ -101,10 +110,30 @@ __global__ __launch_bounds__(EG_LANES) void xfg_egress_kernel(const xfg_egress_k
 				agg += s_cnt[k * EG_WAVES + w];
 			}
 		}
+		// XFG_EGRESS_MULTIBUF: only a packet's first record is swapped -- record
+		// 0, or one whose predecessor has XDP_PKT_CONTD clear (the neighbouring
+		// lane's bit of a ballot; a wave's lane 0 loads record i - 1's options)
+		uint32_t cont = 0;   // bit k: the record of pass k continues a packet
+		if (a.swap_macs && a.multibuf) {
+#pragma unroll
+			for (int k = 0; k < EG_PASSES; k++) {
+				const uint64_t i = i0 + (uint64_t)k * EG_LANES;
+				const uint64_t c = __ballot(rec[k].w & EG_CONTD);
+				uint32_t prev = (uint32_t)(c >> ((lane - 1) & 63)) & 1;
+				if (lane == 0) {
+					prev = 0;
+					if (i < n && i > 0)
+						prev = *reinterpret_cast<eg_gu32 *>(
+							rx + 16ull * ((a.rx_first + (uint32_t)i - 1u) & a.rx_mask) +
+							12) & EG_CONTD;
+				}
+				cont |= prev << k;
+			}
+		}
 		if (a.swap_macs) {
 #pragma unroll
 			for (int k = 0; k < EG_PASSES; k++) {
-				if (vb[k] != A_PASS)
+				if (vb[k] != A_PASS || ((cont >> k) & 1))
 					continue;
 				const uint64_t addr = (uint64_t)rec[k].y << 32 | rec[k].x;
 				gu32x4_w *p = reinterpret_cast<gu32x4_w *>(umem + (addr & EG_ADDR) +
@@ -150,6 +179,9 @@ __global__ __launch_bounds__(EG_LANES) void xfg_egress_kernel(const xfg_egress_k
 		}
 		__syncthreads();
 		const uint32_t base = s_base;
+		// a TX record's options: 0, or with XFG_EGRESS_MULTIBUF eop ? 0 :
+		// XDP_PKT_CONTD (lib/util/xdpsock.c:1528)
+		const uint32_t keep = a.multibuf ? EG_CONTD : 0u;
 #pragma unroll
 		for (int k = 0; k < EG_PASSES; k++) {
 			const uint64_t i = i0 + (uint64_t)k * EG_LANES;
@@ -158,7 +190,7 @@ __global__ __launch_bounds__(EG_LANES) void xfg_egress_kernel(const xfg_egress_k
 			const uint32_t np = base + before[k];   // PASS frames before packet i
 			if (vb[k] == A_PASS) {
 				*reinterpret_cast<gdesc_w *>(tx + 16ull * ((a.tx_first + np) & a.tx_mask)) =
-					u32x4{ rec[k].x, rec[k].y, rec[k].z, 0 };
+					u32x4{ rec[k].x, rec[k].y, rec[k].z, rec[k].w & keep };
 			} else if (fill) {
 				const uint64_t addr = (uint64_t)rec[k].y << 32 | rec[k].x;
 				*reinterpret_cast<gu64_w *>(

@@ -2228,4 +2228,8 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // over bytes
 #include "xfg_capture.hip"
 
+// multi-buffer AF_XDP packets (head pass, verdict spread): the egress
+// kernel's scheme over the end-of-packet flags
+#include "xfg_frags.hip"
+
 #endif   // XFG_PART_COMMON

@@ -308,6 +308,9 @@ struct xfg_egress_kargs {
 	uint32_t fill_first, fill_mask;
 	uint32_t n;                     /* packets, >= 1 */
 	uint32_t swap_macs;
+	/* XFG_EGRESS_MULTIBUF: a TX record keeps XDP_PKT_CONTD, the swap touches
+	 * head records only (the record before has the bit clear) */
+	uint32_t multibuf;
 };
 #define XFG_EGRESS_TILE 2048u   /* packets a tile: 256 lanes x 8 passes */
 #define XFG_EGRESS_TILES(n) (((uint64_t)(n) + XFG_EGRESS_TILE - 1) / XFG_EGRESS_TILE)
@@ -343,6 +346,25 @@ struct xfg_capture_kargs {
 #define XFG_CAPTURE_TILE 2048u   /* packets a tile: 256 lanes x 8 passes */
 #define XFG_CAPTURE_TILES(n) (((uint64_t)(n) + XFG_CAPTURE_TILE - 1) / XFG_CAPTURE_TILE)
 #define XFG_CAPTURE_STATE_WORDS(n) ((XFG_CAPTURE_TILES(n) + 3) & ~1ull)
+
+/* Arguments of the head pass over a multi-buffer RX batch (xfg_frags.hip,
+ * xfg_classify_descs_frags()): the RX records, record i's packet index
+ * pkt_of[i] (end-of-packet records before i), the head records copied to
+ * heads[pkt_of[i]] (room for n), and the launch's state words -- word 0 the
+ * tile ticket, word 2 the packets (end-of-packet records), word 3 the records
+ * in complete packets (the last end-of-packet index + 1), from word 4 one
+ * status word a tile; zeroed by the launch function. */
+struct xfg_frags_kargs {
+	const void *rx;
+	uint32_t *pkt_of;
+	void *heads;
+	unsigned long long *state;
+	uint32_t first, mask;
+	uint32_t n;                     /* records, >= 1 */
+};
+#define XFG_FRAGS_TILE 2048u   /* records a tile: 256 lanes x 8 passes */
+#define XFG_FRAGS_TILES(n) (((uint64_t)(n) + XFG_FRAGS_TILE - 1) / XFG_FRAGS_TILE)
+#define XFG_FRAGS_STATE_WORDS(n) ((XFG_FRAGS_TILES(n) + 5) & ~1ull)
 
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)

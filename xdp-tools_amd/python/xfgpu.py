@@ -62,9 +62,12 @@ EXPORTS = [
     "xfg_comm_unique_id", "xfg_comm_init", "xfg_comm_allreduce", "xfg_map_update_batch_percpu",
     "xfg_classify_descs", "xfg_compact", "xfg_classify_xsk_host", "xfg_host_register",
     "xfg_host_unregister", "xfg_last_path", "xfg_host_threads", "xfg_classify_descs_timed",
-    "xfg_ring_egress", "xfg_capture", "xfg_capture_descs",
+    "xfg_ring_egress", "xfg_capture", "xfg_capture_descs", "xfg_classify_descs_frags",
+    "xfg_classify_descs_frags_timed",
 ]
 EGRESS_SWAP_MACS = 1
+EGRESS_MULTIBUF = 4
+XDP_PKT_CONTD = 1
 # include/xdpfilter_io.h
 IO_EXPORTS = [
     "xfg_pcap_read", "xfg_host_batch_free", "xfg_pcapng_write_verdicts", "xfg_store_map_name",
@@ -104,6 +107,11 @@ class Egress(C.Structure):
                 ("tx_descs", C.c_void_p), ("tx_first", C.c_uint32), ("tx_mask", C.c_uint32),
                 ("fill_addrs", C.c_void_p), ("fill_first", C.c_uint32), ("fill_mask", C.c_uint32),
                 ("count", C.c_uint64), ("counts", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class Frags(C.Structure):
+    """struct xfg_frags (xfg_classify_descs_frags)."""
+    _fields_ = [("sz", C.c_size_t), ("pkt_of", C.c_void_p), ("counts", C.c_uint64 * 3)]
 
 
 class Capture(C.Structure):
@@ -164,6 +172,11 @@ def _load():
         "xfg_classify": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, vp]),
         "xfg_classify_host": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp]),
         "xfg_classify_descs": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp, vp]),
+        "xfg_classify_descs_frags": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch),
+                                               C.POINTER(Frags), vp, vp]),
+        "xfg_classify_descs_frags_timed": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch),
+                                                     C.POINTER(Frags), vp,
+                                                     C.POINTER(C.c_double)]),
         "xfg_classify_xsk_host": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), C.c_uint64, vp]),
         "xfg_host_register": (C.c_int, [vp, vp, C.c_size_t]),
         "xfg_host_unregister": (C.c_int, [vp, vp]),
@@ -501,6 +514,29 @@ class Filter:
         _check(lib.xfg_classify_descs_timed(self.ctx, dev, C.byref(b), verdicts_ptr, iters,
                                             C.byref(ms)), "classify_descs_timed")
         return ms.value
+
+    def classify_descs_frags(self, umem_ptr, descs_ptr, count, verdicts_ptr, pkt_of_ptr=None,
+                             first=0, mask=0xffffffff, dev=0, stream=None):
+        """A descriptor batch whose packets may span several records
+        (XDP_PKT_CONTD): one verdict byte per record of a complete packet,
+        from its head record (xfg_classify_descs_frags).  Returns the counts
+        (packets, records in them, records of the trailing incomplete one)."""
+        b = DescBatch(umem_ptr, descs_ptr, first, mask, count)
+        fr = Frags(C.sizeof(Frags), pkt_of_ptr)
+        _check(lib.xfg_classify_descs_frags(self.ctx, dev, C.byref(b), C.byref(fr), verdicts_ptr,
+                                            stream), "classify_descs_frags")
+        return tuple(int(c) for c in fr.counts)
+
+    def classify_descs_frags_timed(self, umem_ptr, descs_ptr, count, verdicts_ptr,
+                                   pkt_of_ptr=None, first=0, mask=0xffffffff, dev=0):
+        """One such call with its steps timed: (counts, (head pass ms,
+        classify ms, spread ms)) (xfg_classify_descs_frags_timed)."""
+        b = DescBatch(umem_ptr, descs_ptr, first, mask, count)
+        fr = Frags(C.sizeof(Frags), pkt_of_ptr)
+        ms = (C.c_double * 3)()
+        _check(lib.xfg_classify_descs_frags_timed(self.ctx, dev, C.byref(b), C.byref(fr),
+                                                  verdicts_ptr, ms), "classify_descs_frags_timed")
+        return tuple(int(c) for c in fr.counts), tuple(ms)
 
     def host_register(self, arr: np.ndarray):
         """Pin and map a long-lived host array: the kernels read batches in it
