@@ -446,6 +446,122 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e,
 		    const uint8_t *verdicts, void *stream);
 
 /*
+ * Many sockets over one UMEM: one classify and one egress for a whole poll
+ * round.  An AF_XDP application has one socket per NIC queue over a shared
+ * UMEM (lib/util/xdpsock.c:1788-1809) and peeks a small batch (batch_size 64,
+ * lib/util/xdpsock.c:1682) from each on every round: xsk_l2fwd_all() loops
+ * l2fwd() and xsk_rx_drop_all() loops rx_drop() over the num_socks sockets
+ * (lib/util/xdpsock.c:1553-1576,1269-1285).  With the per-ring calls above
+ * that is one classify and one egress launch a socket, each with a fixed cost
+ * far above the work of 64 records; these two calls take all the sockets'
+ * batches at once.
+ *
+ * struct xfg_socks names the sockets: socks is HOST memory, nsocks entries,
+ * and may be reused as soon as a call returns (the library keeps its own copy
+ * for the device).  Socket s's batch is the count records rx_descs[(rx_first
+ * + i) & rx_mask], i < count, as for xfg_classify_descs; count 0 is allowed.
+ * With base[s] the sum of count over the sockets before s and total =
+ * base[nsocks] (below 2^32), flat packet base[s] + i is socket s's record i.
+ * The caller knows every base[s] from its own counts.
+ *
+ * xfg_classify_socks: the effect of xfg_classify_descs on the plain array of
+ * the total records in flat order -- @verdicts is device memory, total bytes,
+ * in flat order; verdicts, rule hit counts and per-action statistics are
+ * exactly those of nsocks xfg_classify_descs calls, one a socket.  A record is
+ * taken as a whole packet (XDP_PKT_CONTD is not looked at).  One kernel
+ * gathers the records into a plain descriptor array -- flat (device, total x
+ * 16 bytes, 16-byte aligned) when given, else library scratch -- and that
+ * array is classified as xfg_classify_descs classifies one of total records:
+ * every kernel stays available, xfg_open_opts.descs_min_packets and
+ * xfg_last_path behave as for such a call.  A flat array the caller passes is
+ * a finished plain descriptor array when the call's work is done:
+ * xfg_capture_descs with mask 0xffffffff, xfg_compact over the verdicts and
+ * any other per-record call compose with it as they are.
+ *
+ * xfg_socks_egress: l2fwd() a socket (lib/util/xdpsock.c:1466-1551), all of
+ * them in one launch.  The k-th record of socket s, in its own order, whose
+ * verdict is XFG_XDP_PASS becomes tx_descs[(tx_first + k) & tx_mask] of that
+ * socket: addr and len as received, options 0.  A socket with tx_descs == NULL
+ * sends nothing and all its chunks go to the fill side (rx_drop,
+ * lib/util/xdpsock.c:1199-1258); its verdicts are not read.  Every other
+ * record hands its chunk back, addr & ((1 << 48) - 1):
+ *   shared fill ring (e->fill_addrs != NULL, the reference's one umem->fq):
+ *     the j-th such record in flat order goes to e->fill_addrs[(e->fill_first
+ *     + j) & e->fill_mask]; the sockets' own fill fields are ignored;
+ *   per-socket fill rings (e->fill_addrs == NULL; a socket per queue, each
+ *     with its own fill ring, xsk_socket__create_shared()): the j-th such
+ *     record of socket s goes to that socket's fill_addrs[(fill_first + j) &
+ *     fill_mask]; a socket whose fill_addrs is NULL writes none.
+ * counts (device, (2 * nsocks + 2) x u64): counts[2s] socket s's TX records,
+ * counts[2s + 1] its other records (in either mode, written or not),
+ * counts[2 * nsocks] and [2 * nsocks + 1] the two totals.  Ring entries past
+ * those counts are not written.  XFG_EGRESS_SWAP_MACS as for xfg_ring_egress
+ * (the records that go to a TX ring; e needs sk->umem then).  @verdicts is the
+ * flat array xfg_classify_socks wrote.
+ *
+ * Masks, index wrap and ring overlap are as for xfg_ring_egress.  Each ring
+ * that is written needs at least as many entries as can reach it: its socket's
+ * count, or total for the shared fill ring.
+ *
+ * Both calls are stream-ordered on @stream (NULL: the library's stream of the
+ * device) and make no host synchronisation: classify then egress on one
+ * stream need none between them.  (The socket table reaches the device
+ * through a small ring of pinned staging slots; the host waits only if all of
+ * them are still in flight.)
+ *
+ * -EINVAL, both calls: sk == NULL, sz below the structure's size, socks ==
+ * NULL, nsocks == 0 or above XFG_SOCKS_MAX, a socket with count != 0 and a
+ * NULL or not 8-byte aligned rx_descs, an rx_mask that is not 2^k - 1, count
+ * > rx_mask + 1, total >= 2^32.  xfg_classify_socks: umem or verdicts NULL
+ * with total != 0, flat not 16-byte aligned.  xfg_socks_egress: e == NULL, sz
+ * below the structure's size, counts NULL or not 8-byte aligned, a flag other
+ * than XFG_EGRESS_SWAP_MACS (XFG_EGRESS_MULTIBUF too), SWAP_MACS without
+ * sk->umem, a ring that is written with a mask that is not 2^k - 1, fewer
+ * entries than can reach it or a pointer that is not 8-byte aligned, verdicts
+ * NULL where a socket with records has a TX ring.  -ENODEV on a host-only
+ * context (after these checks; no device pointer is dereferenced before it).
+ * total == 0: xfg_classify_socks launches nothing and changes no statistic,
+ * xfg_socks_egress writes zero counts and nothing else.
+ *
+ * Not covered: multi-buffer packets across sockets (a socket bound with
+ * XDP_USE_SG keeps its own xfg_classify_descs_frags and xfg_ring_egress
+ * calls), sockets over different UMEMs (one call a UMEM), the host-memory
+ * path (xfg_classify_xsk_host) and the CLI.
+ */
+#define XFG_SOCKS_MAX 1024u
+
+struct xfg_sock {               /* one socket: its peeked RX batch, its TX ring, its fill ring */
+	const void *rx_descs;
+	uint32_t rx_first, rx_mask;
+	void *tx_descs;         /* read by xfg_socks_egress only; NULL: nothing sent */
+	uint32_t tx_first, tx_mask;
+	uint64_t *fill_addrs;   /* read by xfg_socks_egress in per-socket fill mode only */
+	uint32_t fill_first, fill_mask;
+	uint32_t count;         /* records peeked from this socket; 0 is allowed */
+};
+
+struct xfg_socks {
+	size_t sz;                      /* sizeof(struct xfg_socks), for extension */
+	const void *umem;               /* device: the UMEM all sockets share */
+	const struct xfg_sock *socks;   /* HOST memory, nsocks entries */
+	void *flat;                     /* device, total x 16 bytes, or NULL: library scratch */
+	uint32_t nsocks;                /* 1 .. XFG_SOCKS_MAX */
+};
+
+struct xfg_socks_egress {
+	size_t sz;                      /* sizeof(struct xfg_socks_egress), for extension */
+	uint64_t *fill_addrs;           /* the shared fill ring, or NULL: every socket's own */
+	uint32_t fill_first, fill_mask;
+	uint64_t *counts;               /* device, (2 * nsocks + 2) x u64 */
+	uint32_t flags;                 /* XFG_EGRESS_SWAP_MACS only */
+};
+
+int xfg_classify_socks(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+		       uint8_t *verdicts, void *stream);
+int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+		     const struct xfg_socks_egress *e, const uint8_t *verdicts, void *stream);
+
+/*
  * Capture by verdict: the frames of a device-resident batch that a program
  * dropped (or passed, or aborted), as finished pcapng Enhanced Packet Blocks
  * in one contiguous device buffer -- what xdpdump records at a program's exit

@@ -39,6 +39,12 @@
       the whole call (wall clock to its return, and to the stream's end), the
       egress with XFG_EGRESS_MULTIBUF timed as c3f's legs are, and c3d
       (xfg_classify_descs_timed) on the same heads for comparison
+  c3s  C3's rules and frames in c3d's UMEM, scattered over --socks sockets of
+      --batch records (64 x 64 by default; --sweep: 4, 64, 1024 sockets x 64,
+      256 records): a poll round as xfg_classify_descs + xfg_ring_egress a
+      socket beside one xfg_classify_socks + one xfg_socks_egress, whole rounds
+      by host wall clock (the cost at issue is the calls' own), us a round,
+      Mpps and the ratio
 
   c1 xdpfilt_alw_eth, the 8 MAC rules 02:00:00:00:00:0{1..8} (4 dst, 4
       src), 64 B Ethernet/IPv4/UDP frames, 25% carrying a ruled MAC (SURVEY.md
@@ -125,7 +131,7 @@ def run_c1(args):
 C3D_CHUNK, C3D_HEADROOM = 2048, 256
 
 
-def c3d_workload(args, tag, umem_chunks=1):
+def c3d_workload(args, tag, umem_chunks=1, log2_default=22, descs_min_packets=1):
     """C3's frames in a device UMEM behind an RX ring that wraps, the rules
     loaded (c3d, c3f).  Returns a namespace of what the legs use.
     umem_chunks: the UMEM's chunks per frame (c3m's continuation chunks lie
@@ -134,7 +140,7 @@ def c3d_workload(args, tag, umem_chunks=1):
     import numpy as np
     import xftools as X
     import xfgpu as G
-    n = 1 << (args.log2_packets or 22)
+    n = 1 << (args.log2_packets or log2_default)
     n4, nports, stride = 1_000_000, 16, 64
     t0 = time.time()
     v4 = X.rand_keys(3, int(n4 * 1.02) + 16, 4)[:n4]
@@ -143,7 +149,7 @@ def c3d_workload(args, tag, umem_chunks=1):
     # (descs_min_packets=1: the pipelined descriptor mode at any --log2-packets,
     # also below the size from which xfg_classify_descs takes it by default)
     f = G.Filter(G.FEAT_ALL | G.FEAT_DENY, devices=[0], ipv4_capacity=n4, ipv6_capacity=1024,
-                 descs_min_packets=1)
+                 descs_min_packets=descs_min_packets)
     f.update_batch(G.MAP_IPV4, v4, np.full(len(v4), 2, np.uint64))
     pk = np.array([X.port_key(int(p)) for p in ports], "<u4").view(np.uint8)
     f.update_batch(G.MAP_PORTS, pk, np.full(len(ports), 2 | 4 | 8, np.uint64))
@@ -512,10 +518,113 @@ def run_c3m(args):
     print(json.dumps(line), flush=True)
 
 
+def run_c3s(args):
+    """C3's rules and frames in a UMEM, scattered over S sockets of B records
+    (a poll round of an application with a socket a NIC queue): the round as
+    the per-ring calls make it -- xfg_classify_descs and xfg_ring_egress a
+    socket, 2 S calls -- beside one xfg_classify_socks and one
+    xfg_socks_egress.  Whole rounds by host wall clock, one xfg_sync at the end
+    of a leg's run; the legs alternate, args.runs runs each.  The context keeps
+    the default descs_min_packets, so either leg's classify takes the kernel a
+    caller would get."""
+    import ctypes as C
+    import statistics
+    import numpy as np
+    import xfgpu as G
+    points = ([(s, b) for b in (64, 256) for s in (4, 64, 1024)] if args.sweep
+              else [(args.socks, args.batch)])
+    most = max(s * b for s, b in points)
+    w = c3d_workload(args, "c3s", log2_default=max(12, (most - 1).bit_length()), descs_min_packets=0)
+    f = w.f
+    assert most <= w.n, "more records than --log2-packets frames"
+    for S, B in points:
+        n, R = S * B, 2 * B                    # every ring twice the batch, wrapping inside it
+        first = R - 7
+        # socket s's RX ring: frames s * B .. of the workload, C3D's chunk addresses
+        descs = np.zeros((S, R, 2), np.uint64)
+        idx = (first + np.arange(B)) & (R - 1)
+        addr = w.perm[:n].astype(np.uint64) * np.uint64(C3D_CHUNK) + np.uint64(C3D_HEADROOM)
+        descs[:, idx, 0] = addr.reshape(S, B)
+        descs[:, idx, 1] = w.lens[:n].astype(np.uint64).reshape(S, B)
+        d_rx, d_tx, d_fill = f.alloc(descs.nbytes), f.alloc(16 * S * R), f.alloc(8 * S * R)
+        d_v = [f.alloc(n), f.alloc(n)]
+        d_c = [f.alloc(16 * S), f.alloc(8 * (2 * S + 2))]
+        d_rx.upload(descs)
+        rings = [dict(rx_descs=d_rx.ptr + 16 * R * s, rx_first=first, rx_mask=R - 1,
+                      tx_descs=d_tx.ptr + 16 * R * s, tx_first=R - 5, tx_mask=R - 1,
+                      fill_addrs=d_fill.ptr + 8 * R * s, fill_first=R - 3, fill_mask=R - 1, count=B)
+                 for s in range(S)]
+        # leg 1: the structures of every call built once, the library called directly
+        per = []
+        for s, r in enumerate(rings):
+            db = G.DescBatch(w.d_umem.ptr, r["rx_descs"], first, R - 1, B)
+            e = G.Egress(C.sizeof(G.Egress), None, r["rx_descs"], first, R - 1, r["tx_descs"],
+                         r["tx_first"], R - 1, r["fill_addrs"], r["fill_first"], R - 1, B,
+                         d_c[0].ptr + 16 * s, 0)
+            per.append((C.byref(db), C.byref(e), d_v[0].ptr + s * B, db, e))
+        tab = G.sock_table(rings)
+        sk = G.Socks(C.sizeof(G.Socks), w.d_umem.ptr, tab, None, S)
+        se = G.SocksEgress(C.sizeof(G.SocksEgress), None, 0, 0, d_c[1].ptr, 0)
+        lib, ctx = G.lib, f.ctx
+
+        def loop_round():
+            for db, e, v, _, _ in per:
+                rc = lib.xfg_classify_descs(ctx, 0, db, v, None) or lib.xfg_ring_egress(ctx, 0, e, v, None)
+                assert rc == 0, rc
+
+        def single_round():
+            rc = (lib.xfg_classify_socks(ctx, 0, C.byref(sk), d_v[1].ptr, None) or
+                  lib.xfg_socks_egress(ctx, 0, C.byref(sk), C.byref(se), d_v[1].ptr, None))
+            assert rc == 0, rc
+
+        legs = {"per_socket_loop": loop_round, "single_call": single_round}
+        rounds, us, paths = {}, {k: [] for k in legs}, {}
+        for k, one in legs.items():                 # warm-up, and how many rounds a run needs
+            for _ in range(3):
+                one()
+            f.sync()
+            t0 = time.perf_counter()
+            for _ in range(3):
+                one()
+            f.sync()
+            rounds[k] = int(min(2000, max(5, 0.1 / ((time.perf_counter() - t0) / 3))))
+            paths[k] = f.last_path()
+        for _ in range(max(1, args.runs)):
+            for k, one in legs.items():
+                t0 = time.perf_counter()
+                for _ in range(rounds[k]):
+                    one()
+                f.sync()
+                us[k].append((time.perf_counter() - t0) / rounds[k] * 1e6)
+        # both legs computed the same round
+        v0, v1 = (d.download(np.zeros(n, np.uint8)) for d in d_v)
+        assert np.array_equal(v0, v1)
+        c0 = d_c[0].download(np.zeros(2 * S, np.uint64))
+        c1 = d_c[1].download(np.zeros(2 * S + 2, np.uint64))
+        assert np.array_equal(c0, c1[:2 * S]) and int(c1[2 * S]) == int(np.count_nonzero(v1 == 2))
+        line = {"config": "c3s", "program": f.prog_name, "socks": S, "batch": B, "packets": n,
+                "rules_ipv4": w.n4, "port_rules": w.nports, "pass_frames": int(c1[2 * S]),
+                "calls_per_round": {"per_socket_loop": 2 * S, "single_call": 2}}
+        for k in legs:
+            med = statistics.median(us[k])
+            line[k] = {"us_per_round": [round(u, 1) for u in us[k]], "median_us": round(med, 1),
+                       "Mpps": round(n / med, 2), "rounds_per_run": rounds[k],
+                       "spread": round((max(us[k]) - min(us[k])) / med, 3), "kernel_path": paths[k]}
+        line["ratio"] = round(line["per_socket_loop"]["median_us"] / line["single_call"]["median_us"], 2)
+        # faster by more than the runs of either leg differ among themselves
+        line["single_call_faster_beyond_spread"] = bool(max(us["single_call"]) < min(us["per_socket_loop"]))
+        print(json.dumps(line), flush=True)
+        for b in [d_rx, d_tx, d_fill] + d_v + d_c:
+            b.free()
+    f.close()
+
+
 def run(name, args):
     import numpy as np
     import xftools as X
     import xfgpu as G
+    if name == "c3s":
+        return run_c3s(args)
     if name == "c1":
         return run_c1(args)
     if name == "c3c":
@@ -622,6 +731,11 @@ def main():
     ap.add_argument("--no-host", action="store_true",
                     help="c5: the device-resident leg only (PMC passes of its kernel)")
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--socks", type=int, default=64, help="c3s: sockets a round")
+    ap.add_argument("--batch", type=int, default=64,
+                    help="c3s: records peeked from each socket (a power of two)")
+    ap.add_argument("--sweep", action="store_true",
+                    help="c3s: sockets 4, 64, 1024 x batch 64, 256 instead of one point")
     a = ap.parse_args()
     for c in a.configs:
         run(c, a)

@@ -46,6 +46,8 @@ int xfg_launch_capture(const struct xfg_capture_kargs *a, unsigned grid, void *s
 int xfg_launch_frags_heads(const struct xfg_frags_kargs *a, unsigned grid, void *stream);
 int xfg_launch_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *verdicts,
 			    uint32_t done, unsigned grid, void *stream);
+int xfg_launch_socks_gather(const struct xfg_socks_gather_kargs *a, unsigned grid, void *stream);
+int xfg_launch_socks_egress(const struct xfg_socks_kargs *a, unsigned grid, void *stream);
 int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 		       unsigned long long *hits, uint32_t n, void *stream);
 
@@ -57,6 +59,11 @@ int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 #ifndef HOST_SLOTS
 #define HOST_SLOTS 4
 #endif
+/* many sockets (xfg_classify_socks, xfg_socks_egress): socket tables on their
+ * way to the device at one time; a slot holds the largest table */
+#define SOCKS_SLOTS 8
+#define SOCKS_SLOT_BYTES ((XFG_SOCKS_TABLE_BYTES(XFG_SOCKS_MAX) + 63) & ~63ull)
+_Static_assert(XFG_SOCKS_MAX == XFG_SOCKS_TABLE_MAX, "the kernels' table of bases");
 
 struct dev_map {           /* device arrays of one hash map */
 	uint8_t *buckets;      /* (nbuckets + 1) * 64 B: keys, per-device flags, meta */
@@ -155,6 +162,20 @@ struct xfg_dev {
 	uint8_t *fr_pv;
 	uint32_t *fr_pkt;
 	uint64_t fr_heads_bytes, fr_pv_bytes, fr_pkt_bytes;
+	/* many sockets (xfg_classify_socks, xfg_socks_egress).  The caller's
+	 * socket table is host memory it may reuse when a call returns, so each
+	 * call copies it (rings and bases, xfg_layout.h) into the next of a ring
+	 * of pinned staging slots and from there to the slot's device copy on
+	 * the device's stream; the slot's event, recorded behind the kernel that
+	 * reads the table, says when both may be written again (under d->lock;
+	 * made at first use).  One xfg_classify_socks at a time under
+	 * socks_lock: the gathered records where the caller passes no array. */
+	pthread_mutex_t socks_lock;
+	uint8_t *sk_host[SOCKS_SLOTS], *sk_dev[SOCKS_SLOTS];
+	hipEvent_t sk_done[SOCKS_SLOTS];
+	uint32_t sk_next;
+	void *sk_flat;
+	uint64_t sk_flat_bytes;
 	hipEvent_t ev_user, ev_done;    /* ordering against a caller's stream */
 };
 
@@ -407,6 +428,7 @@ static void dev_free(struct xfg_dev *d)
 		pthread_mutex_destroy(&d->lock);
 		pthread_mutex_destroy(&d->host_lock);
 		pthread_mutex_destroy(&d->frags_lock);
+		pthread_mutex_destroy(&d->socks_lock);
 		d->lock_ok = 0;
 	}
 	if (hipSetDevice(d->ordinal) != hipSuccess)
@@ -465,6 +487,13 @@ static void dev_free(struct xfg_dev *d)
 	hipFree(d->fr_heads);
 	hipFree(d->fr_pv);
 	hipFree(d->fr_pkt);
+	for (int k = 0; k < SOCKS_SLOTS; k++) {
+		hipHostFree(d->sk_host[k]);
+		hipFree(d->sk_dev[k]);
+		if (d->sk_done[k])
+			hipEventDestroy(d->sk_done[k]);
+	}
+	hipFree(d->sk_flat);
 	if (d->ev_user)
 		hipEventDestroy(d->ev_user);
 	if (d->ev_done)
@@ -485,6 +514,7 @@ static int dev_init(xfg_ctx *ctx, struct xfg_dev *d)
 	pthread_mutex_init(&d->lock, NULL);
 	pthread_mutex_init(&d->host_lock, NULL);
 	pthread_mutex_init(&d->frags_lock, NULL);
+	pthread_mutex_init(&d->socks_lock, NULL);
 	d->lock_ok = 1;
 	HIPCHK(hipSetDevice(d->ordinal));
 	HIPCHK(hipGetDeviceProperties(&prop, d->ordinal));
@@ -2182,6 +2212,198 @@ int xfg_classify_descs_frags_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_
 	if (!ms)
 		return -EINVAL;
 	return frags_run(ctx, dev, db, fr, verdicts, NULL, ms);
+}
+
+/* Many sockets over one UMEM (include/xdpfilter_gpu.h): what both calls check
+ * of the sockets; *total their records. */
+static int socks_check(const struct xfg_socks *sk, uint64_t *total)
+{
+	if (!sk || sk->sz < sizeof(*sk) || !sk->socks || !sk->nsocks || sk->nsocks > XFG_SOCKS_MAX)
+		return -EINVAL;
+	uint64_t n = 0;
+	for (uint32_t s = 0; s < sk->nsocks; s++) {
+		const struct xfg_sock *k = &sk->socks[s];
+		if (!mask_ok(k->rx_mask) || (uint64_t)k->rx_mask + 1 < k->count)
+			return -EINVAL;
+		if (k->count && (!k->rx_descs || ((uintptr_t)k->rx_descs & 7)))
+			return -EINVAL;
+		n += k->count;
+	}
+	if (n > 0xffffffffull)
+		return -EINVAL;
+	*total = n;
+	return 0;
+}
+
+/* The socket table of @sk on its way to the device (d->lock held, the device
+ * current): into the next staging slot -- waiting for the slot's last user,
+ * SOCKS_SLOTS calls ago, only if that is still in flight -- and from there to
+ * the slot's device copy on the device's stream.  The caller launches the
+ * kernel that reads it and then calls socks_table_done(). */
+static int socks_table(struct xfg_dev *d, const struct xfg_socks *sk, int *slot,
+		       const struct xfg_sock_ent **ents, const uint32_t **base)
+{
+	int err = 0;
+	const int k = (int)d->sk_next;
+	if (!d->sk_host[k])
+		HIPCHK(hipHostMalloc((void **)&d->sk_host[k], SOCKS_SLOT_BYTES, hipHostMallocDefault));
+	if (!d->sk_dev[k])
+		HIPCHK(hipMalloc((void **)&d->sk_dev[k], SOCKS_SLOT_BYTES));
+	if (!d->sk_done[k])
+		HIPCHK(hipEventCreateWithFlags(&d->sk_done[k], hipEventDisableTiming));
+	HIPCHK(hipEventSynchronize(d->sk_done[k]));
+	struct xfg_sock_ent *he = (struct xfg_sock_ent *)d->sk_host[k];
+	uint32_t *hb = (uint32_t *)(he + sk->nsocks);
+	uint32_t n = 0;
+	for (uint32_t s = 0; s < sk->nsocks; s++) {
+		const struct xfg_sock *q = &sk->socks[s];
+		he[s].rx = (struct xfg_sock_ring){ (uintptr_t)q->rx_descs, q->rx_first, q->rx_mask };
+		he[s].tx = (struct xfg_sock_ring){ (uintptr_t)q->tx_descs, q->tx_first, q->tx_mask };
+		he[s].fill = (struct xfg_sock_ring){ (uintptr_t)q->fill_addrs, q->fill_first, q->fill_mask };
+		hb[s] = n;
+		n += q->count;
+	}
+	hb[sk->nsocks] = n;
+	HIPCHK(hipMemcpyAsync(d->sk_dev[k], d->sk_host[k], XFG_SOCKS_TABLE_BYTES(sk->nsocks),
+			      hipMemcpyHostToDevice, d->stream));
+	d->sk_next = (uint32_t)(k + 1) % SOCKS_SLOTS;
+	*slot = k;
+	*ents = (const struct xfg_sock_ent *)d->sk_dev[k];
+	*base = (const uint32_t *)(*ents + sk->nsocks);
+fail:
+	return err;
+}
+
+/* ... behind that kernel (or behind the copy alone, if its launch failed). */
+static int socks_table_done(struct xfg_dev *d, int slot)
+{
+	return hip_err(hipEventRecord(d->sk_done[slot], d->stream));
+}
+
+/* One classify for the sockets' batches: the gather kernel, then classify()
+ * over the flat array as xfg_classify_descs runs it.  All of it on the
+ * device's own stream, after @stream's earlier work and before its later, with
+ * no host synchronisation; socks_lock keeps a second caller off the flat
+ * scratch between the two steps (d->lock itself is released for classify(),
+ * which takes it), as frags_lock does in frags_run(). */
+int xfg_classify_socks(xfg_ctx *ctx, int dev, const struct xfg_socks *sk, uint8_t *verdicts,
+		       void *stream)
+{
+	uint64_t total = 0;
+	int err, entered = 0, slot = -1;
+	if (!ctx)
+		return -EINVAL;
+	if ((err = socks_check(sk, &total)))
+		return err;
+	if (((uintptr_t)sk->flat & 15) || (total && (!sk->umem || !verdicts)))
+		return -EINVAL;
+	if (!ctx->ndev)
+		return -ENODEV;
+	if (dev < 0 || dev >= ctx->ndev)
+		return -EINVAL;
+	if (!total)
+		return 0;
+	struct xfg_dev *d = &ctx->dev[dev];
+	pthread_mutex_lock(&d->socks_lock);
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!sk->flat && (err = scratch(d, &d->sk_flat, &d->sk_flat_bytes, total * 16)))
+		goto fail;
+	struct xfg_socks_gather_kargs a = {
+		.flat = sk->flat ? sk->flat : d->sk_flat, .n = (uint32_t)total, .nsocks = sk->nsocks,
+	};
+	if ((err = stream_enter(d, stream)))
+		goto fail;
+	entered = 1;
+	if ((err = socks_table(d, sk, &slot, &a.ents, &a.base)))
+		goto fail;
+	err = xfg_launch_socks_gather(&a, (unsigned)d->ncu * 8, d->stream);
+	const int e1 = socks_table_done(d, slot);
+	if ((err = err ? err : e1))
+		goto fail;
+	pthread_mutex_unlock(&d->lock);
+	const struct xfg_desc_batch flat = { sk->umem, a.flat, 0, 0xffffffffu, total };
+	err = classify(ctx, dev, NULL, &flat, verdicts, NULL, 1, NULL);
+	pthread_mutex_lock(&d->lock);
+	if (hipSetDevice(d->ordinal) != hipSuccess)
+		err = err ? err : -EIO;
+fail:
+	/* (also after an error: the caller's stream behind what was queued) */
+	if (entered) {
+		const int e2 = stream_leave(d, stream);
+		err = err ? err : e2;
+	}
+	pthread_mutex_unlock(&d->lock);
+	pthread_mutex_unlock(&d->socks_lock);
+	return err;
+}
+
+/* Every socket's TX ring and the fill ring(s) in one launch: like
+ * xfg_ring_egress on the device's own stream between the two events, over the
+ * same status buffer. */
+int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+		     const struct xfg_socks_egress *e, const uint8_t *verdicts, void *stream)
+{
+	uint64_t total = 0;
+	int err, slot = -1;
+	if (!ctx)
+		return -EINVAL;
+	if ((err = socks_check(sk, &total)))
+		return err;
+	if (!e || e->sz < sizeof(*e) || !e->counts || ((uintptr_t)e->counts & 7) ||
+	    (e->flags & ~XFG_EGRESS_SWAP_MACS) || ((uintptr_t)sk->umem & 7) ||
+	    ((e->flags & XFG_EGRESS_SWAP_MACS) && !sk->umem))
+		return -EINVAL;
+	if (e->fill_addrs && (((uintptr_t)e->fill_addrs & 7) || !mask_ok(e->fill_mask) ||
+			      (uint64_t)e->fill_mask + 1 < total))
+		return -EINVAL;
+	for (uint32_t s = 0; s < sk->nsocks; s++) {
+		const struct xfg_sock *k = &sk->socks[s];
+		if (k->tx_descs && (((uintptr_t)k->tx_descs & 7) || !mask_ok(k->tx_mask) ||
+				    (uint64_t)k->tx_mask + 1 < k->count || (k->count && !verdicts)))
+			return -EINVAL;
+		if (!e->fill_addrs && k->fill_addrs &&
+		    (((uintptr_t)k->fill_addrs & 7) || !mask_ok(k->fill_mask) ||
+		     (uint64_t)k->fill_mask + 1 < k->count))
+			return -EINVAL;
+	}
+	if (!ctx->ndev)
+		return -ENODEV;
+	if (dev < 0 || dev >= ctx->ndev)
+		return -EINVAL;
+	struct xfg_dev *d = &ctx->dev[dev];
+	hipStream_t user = (hipStream_t)stream;
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!total) {   /* no scratch: on the caller's stream itself */
+		HIPCHK(hipMemsetAsync(e->counts, 0, (2 * (size_t)sk->nsocks + 2) * 8,
+				      user ? user : d->stream));
+		goto fail;
+	}
+	if ((err = cstatus_room(d, XFG_SOCKS_STATE_WORDS(total, sk->nsocks))))
+		goto fail;
+	struct xfg_socks_kargs a = {
+		.umem = (e->flags & XFG_EGRESS_SWAP_MACS) ? (uint8_t *)(uintptr_t)sk->umem : NULL,
+		.fill = e->fill_addrs, .verdicts = verdicts,
+		.counts = (unsigned long long *)e->counts, .state = d->cstatus,
+		.fill_first = e->fill_first, .fill_mask = e->fill_mask,
+		.n = (uint32_t)total, .nsocks = sk->nsocks,
+		.swap_macs = !!(e->flags & XFG_EGRESS_SWAP_MACS),
+	};
+	if ((err = stream_enter(d, stream)))
+		goto fail;
+	if (!(err = socks_table(d, sk, &slot, &a.ents, &a.base))) {
+		/* (four workgroups a CU: all of them resident) */
+		err = xfg_launch_socks_egress(&a, (unsigned)d->ncu * 4, d->stream);
+		const int e1 = socks_table_done(d, slot);
+		err = err ? err : e1;
+	}
+	/* (also after an error: the caller's stream behind what was queued) */
+	const int e2 = stream_leave(d, stream);
+	err = err ? err : e2;
+fail:
+	pthread_mutex_unlock(&d->lock);
+	return err;
 }
 
 /* Capture by verdict (include/xdpfilter_gpu.h): both entry points fill the

@@ -2232,4 +2232,8 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // kernel's scheme over the end-of-packet flags
 #include "xfg_frags.hip"
 
+// many sockets over one UMEM (gather, segmented egress): the egress kernel's
+// scheme with a socket table in the place of one ring
+#include "xfg_socks.hip"
+
 #endif   // XFG_PART_COMMON

@@ -366,6 +366,55 @@ struct xfg_frags_kargs {
 #define XFG_FRAGS_TILES(n) (((uint64_t)(n) + XFG_FRAGS_TILE - 1) / XFG_FRAGS_TILE)
 #define XFG_FRAGS_STATE_WORDS(n) ((XFG_FRAGS_TILES(n) + 5) & ~1ull)
 
+/* Many sockets over one UMEM (xfg_socks.hip, xfg_classify_socks() and
+ * xfg_socks_egress()).  A socket's three rings as the kernels read them, one
+ * 16-byte load each; a launch's table in device memory is nsocks of these and,
+ * behind them, the nsocks + 1 bases (base[s] = the records of the sockets
+ * before s, base[nsocks] = the total). */
+struct xfg_sock_ring {
+	uint64_t p;                     /* device address, 0: no such ring */
+	uint32_t first, mask;
+};
+struct xfg_sock_ent {
+	struct xfg_sock_ring rx, tx, fill;
+};
+#define XFG_SOCKS_TABLE_MAX 1024u   /* XFG_SOCKS_MAX: the bases fit in LDS */
+#define XFG_SOCKS_TABLE_BYTES(nsocks) \
+	((uint64_t)(nsocks) * sizeof(struct xfg_sock_ent) + ((uint64_t)(nsocks) + 1) * 4)
+
+/* Arguments of the gather kernel: flat[base[s] + i] = socket s's RX record i. */
+struct xfg_socks_gather_kargs {
+	const struct xfg_sock_ent *ents;
+	const uint32_t *base;
+	void *flat;                     /* 16-byte aligned, n records */
+	uint32_t n;                     /* records of all sockets, >= 1 */
+	uint32_t nsocks;
+};
+
+/* Arguments of the segmented egress kernel: the table, the shared fill ring
+ * (NULL: every socket's own) and the launch's state words -- word 0 the tile
+ * ticket, word 1 set by a wait that gave up (XFG_SOCKS_SPINS polls: never in
+ * a run that makes progress), from word 2 one status word a tile, then one
+ * {flag, PASS records before base[s]} word a socket and one for the total;
+ * zeroed by the launch function. */
+struct xfg_socks_kargs {
+	uint8_t *umem;                  /* written only with swap_macs */
+	const struct xfg_sock_ent *ents;
+	const uint32_t *base;
+	uint64_t *fill;
+	const uint8_t *verdicts;
+	unsigned long long *counts;     /* 2 * nsocks + 2 */
+	unsigned long long *state;
+	uint32_t fill_first, fill_mask;
+	uint32_t n;                     /* records of all sockets, >= 1 */
+	uint32_t nsocks;
+	uint32_t swap_macs;
+};
+#define XFG_SOCKS_TILE 2048u   /* records a tile: 256 lanes x 8 passes */
+#define XFG_SOCKS_TILES(n) (((uint64_t)(n) + XFG_SOCKS_TILE - 1) / XFG_SOCKS_TILE)
+#define XFG_SOCKS_STATE_WORDS(n, nsocks) ((XFG_SOCKS_TILES(n) + (uint64_t)(nsocks) + 4) & ~1ull)
+#define XFG_SOCKS_SPINS (1u << 24)
+
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 #define XFG_HD __host__ __device__ __forceinline__

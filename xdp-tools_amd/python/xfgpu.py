@@ -63,8 +63,9 @@ EXPORTS = [
     "xfg_classify_descs", "xfg_compact", "xfg_classify_xsk_host", "xfg_host_register",
     "xfg_host_unregister", "xfg_last_path", "xfg_host_threads", "xfg_classify_descs_timed",
     "xfg_ring_egress", "xfg_capture", "xfg_capture_descs", "xfg_classify_descs_frags",
-    "xfg_classify_descs_frags_timed",
+    "xfg_classify_descs_frags_timed", "xfg_classify_socks", "xfg_socks_egress",
 ]
+SOCKS_MAX = 1024
 EGRESS_SWAP_MACS = 1
 EGRESS_MULTIBUF = 4
 XDP_PKT_CONTD = 1
@@ -112,6 +113,40 @@ class Egress(C.Structure):
 class Frags(C.Structure):
     """struct xfg_frags (xfg_classify_descs_frags)."""
     _fields_ = [("sz", C.c_size_t), ("pkt_of", C.c_void_p), ("counts", C.c_uint64 * 3)]
+
+
+class Sock(C.Structure):
+    """struct xfg_sock: one socket's peeked RX batch, its TX ring, its fill ring."""
+    _fields_ = [("rx_descs", C.c_void_p), ("rx_first", C.c_uint32), ("rx_mask", C.c_uint32),
+                ("tx_descs", C.c_void_p), ("tx_first", C.c_uint32), ("tx_mask", C.c_uint32),
+                ("fill_addrs", C.c_void_p), ("fill_first", C.c_uint32), ("fill_mask", C.c_uint32),
+                ("count", C.c_uint32)]
+
+
+class Socks(C.Structure):
+    """struct xfg_socks (xfg_classify_socks, xfg_socks_egress)."""
+    _fields_ = [("sz", C.c_size_t), ("umem", C.c_void_p), ("socks", C.POINTER(Sock)),
+                ("flat", C.c_void_p), ("nsocks", C.c_uint32)]
+
+
+class SocksEgress(C.Structure):
+    """struct xfg_socks_egress (xfg_socks_egress)."""
+    _fields_ = [("sz", C.c_size_t), ("fill_addrs", C.c_void_p), ("fill_first", C.c_uint32),
+                ("fill_mask", C.c_uint32), ("counts", C.c_void_p), ("flags", C.c_uint32)]
+
+
+def sock_table(socks):
+    """A host socket table (a ctypes array of Sock) from Sock values or dicts of their
+    fields; masks left out are 0xffffffff (plain arrays)."""
+    arr = (Sock * max(len(socks), 1))()
+    for i, s in enumerate(socks):
+        if isinstance(s, Sock):
+            arr[i] = s
+            continue
+        f = dict(rx_mask=0xffffffff, tx_mask=0xffffffff, fill_mask=0xffffffff)
+        f.update(s)
+        arr[i] = Sock(**f)
+    return arr
 
 
 class Capture(C.Structure):
@@ -183,6 +218,9 @@ def _load():
         "xfg_host_threads": (C.c_int, []),
         "xfg_compact": (C.c_int, [vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp, vp]),
         "xfg_ring_egress": (C.c_int, [vp, C.c_int, C.POINTER(Egress), vp, vp]),
+        "xfg_classify_socks": (C.c_int, [vp, C.c_int, C.POINTER(Socks), vp, vp]),
+        "xfg_socks_egress": (C.c_int, [vp, C.c_int, C.POINTER(Socks), C.POINTER(SocksEgress), vp,
+                                       vp]),
         "xfg_capture": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.POINTER(Capture), vp]),
         "xfg_capture_descs": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp, C.POINTER(Capture),
                                         vp]),
@@ -573,6 +611,29 @@ class Filter:
                    tx_mask, fill_ptr, fill_first, fill_mask, count, counts_ptr, flags)
         _check(lib.xfg_ring_egress(self.ctx, dev, C.byref(e), verdicts_ptr, stream),
                "ring_egress")
+
+    def classify_socks(self, umem_ptr, socks, verdicts_ptr, nsocks=None, flat_ptr=None, dev=0,
+                       stream=None):
+        """One classify for the RX batches of many sockets over one UMEM
+        (xfg_classify_socks).  socks: a host table from sock_table() (or what
+        it takes); verdicts in flat order, socket after socket.  The table may
+        be overwritten as soon as this returns."""
+        tab = socks if isinstance(socks, C.Array) else sock_table(socks)
+        sk = Socks(C.sizeof(Socks), umem_ptr, tab, flat_ptr, len(socks) if nsocks is None else nsocks)
+        _check(lib.xfg_classify_socks(self.ctx, dev, C.byref(sk), verdicts_ptr, stream),
+               "classify_socks")
+
+    def socks_egress(self, socks, verdicts_ptr, counts_ptr, nsocks=None, fill_ptr=None,
+                     fill_first=0, fill_mask=0xffffffff, umem_ptr=None, flags=0, dev=0,
+                     stream=None):
+        """Every socket's TX records, and the fill addresses into the shared
+        ring at fill_ptr or (None) every socket's own, in one launch
+        (xfg_socks_egress); counts_ptr: 2 * nsocks + 2 u64 on the device."""
+        tab = socks if isinstance(socks, C.Array) else sock_table(socks)
+        sk = Socks(C.sizeof(Socks), umem_ptr, tab, None, len(socks) if nsocks is None else nsocks)
+        e = SocksEgress(C.sizeof(SocksEgress), fill_ptr, fill_first, fill_mask, counts_ptr, flags)
+        _check(lib.xfg_socks_egress(self.ctx, dev, C.byref(sk), C.byref(e), verdicts_ptr, stream),
+               "socks_egress")
 
     def capture_into(self, batch, verdicts_ptr, action_mask, out_ptr, out_bytes, counts_ptr,
                      snaplen=0, ts_ns_ptr=None, ts0=0, dev=0, stream=None):
