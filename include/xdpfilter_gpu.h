@@ -523,10 +523,11 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e,
  * total == 0: xfg_classify_socks launches nothing and changes no statistic,
  * xfg_socks_egress writes zero counts and nothing else.
  *
- * Not covered: multi-buffer packets across sockets (a socket bound with
- * XDP_USE_SG keeps its own xfg_classify_descs_frags and xfg_ring_egress
- * calls), sockets over different UMEMs (one call a UMEM), the host-memory
- * path (xfg_classify_xsk_host) and the CLI.
+ * Not covered: sockets over different UMEMs (one call a UMEM), the host-memory
+ * path (xfg_classify_xsk_host) and the CLI.  Sockets bound with XDP_USE_SG
+ * (multi-buffer packets) take xfg_classify_socks_frags and
+ * xfg_socks_frags_egress below; these two calls take a record as a whole
+ * packet, and xfg_socks_egress refuses XFG_EGRESS_MULTIBUF.
  */
 #define XFG_SOCKS_MAX 1024u
 
@@ -560,6 +561,110 @@ int xfg_classify_socks(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 		       uint8_t *verdicts, void *stream);
 int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 		     const struct xfg_socks_egress *e, const uint8_t *verdicts, void *stream);
+
+/*
+ * Multi-buffer packets across many sockets: one classify and one egress for a
+ * poll round of sockets bound with XDP_USE_SG.  The bind flag is the
+ * application's -- all of its sockets carry it or none does -- so this is what
+ * a multi-queue application that receives jumbo frames or GRO aggregates calls
+ * in the place of one xfg_classify_descs_frags and one xfg_ring_egress
+ * (XFG_EGRESS_MULTIBUF) a socket, each of the former with a host
+ * synchronisation of its own.
+ *
+ * Sockets and flat order are those of struct xfg_socks above: socket s's batch
+ * is its count records, base[s] the sum of the counts before it, flat record
+ * base[s] + i its record i, total < 2^32.
+ *
+ * Packets are formed per socket, as l2fwd() forms them on each socket's own
+ * ring (lib/util/xdpsock.c:1500-1548).  A packet is a maximal run of
+ * consecutive records of one socket's batch ending at the first record whose
+ * options & XFG_XDP_PKT_CONTD is 0.  Record 0 of every socket starts a packet,
+ * whatever the socket before it ended with; a packet never spans sockets.
+ * done[s] is the index + 1 of socket s's last end-of-packet record, 0 if it
+ * has none and 0 for an empty socket.  Socket s's records i >= done[s] are its
+ * trailing incomplete packet: they are not processed -- no verdict, no rule
+ * hit, no statistic -- and the caller leaves them on that ring.
+ *
+ * xfg_classify_socks_frags: verdicts, rule hit counts and per-action
+ * statistics are exactly those of nsocks xfg_classify_descs_frags calls, one a
+ * socket, in socket order.  @verdicts is device memory, total bytes, in flat
+ * order: every record of a complete packet gets its packet's verdict, and
+ * every other record's byte is written as XFG_VERDICT_NONE, so the whole
+ * array is defined.  (A deliberate difference from xfg_classify_descs_frags,
+ * which leaves those bytes alone: xfg_compact and xfg_capture_descs, whose
+ * verdict bytes are below 32, pass over them with nothing added.)  fr->done
+ * (HOST, nsocks x u32) receives done[]: what to xsk_ring_cons__release on each
+ * socket.  fr->counts (HOST): the complete packets, the records in them (the
+ * sum of done[]), the trailing records (total minus that), over all sockets.
+ * fr->pkt_of, when given (device, total x u32): the flat packet index of a
+ * record in a complete packet -- the number of end-of-packet records before it
+ * in flat order -- and XFG_PKT_NONE for the other records.  The packets' head
+ * records are classified as xfg_classify_descs classifies a plain array of
+ * counts[0] records: xfg_open_opts.descs_min_packets, xfg_last_path and every
+ * kernel behave as for such a call.  sk->flat, when given, receives all total
+ * records in flat order as in xfg_classify_socks; when NULL no flat array is
+ * needed at all.
+ *
+ * On the device: a pass that finds done[] (and writes flat), the head pass
+ * (packet indices, the complete packets' heads gathered into library scratch,
+ * the packet count), the read-back of done[] and the packet count, the
+ * classify of the heads, and the spread over all total records -- a number of
+ * launches that does not depend on nsocks.  The read-back is the call's one
+ * host synchronisation, after it has ordered itself behind @stream; the
+ * classify and the spread are stream-ordered after it and the call returns
+ * without waiting for them.  -EIO if a bounded wait on the device gave up:
+ * nothing is classified then and no statistic changes.
+ *
+ * xfg_socks_frags_egress: l2fwd() a socket with its frags handling
+ * (lib/util/xdpsock.c:1521-1542), all sockets in one launch.  sk, e, the fill
+ * modes, the layout of counts, masks, index wrap and ring sizes are those of
+ * xfg_socks_egress; ring sizes are checked against a socket's count, not its
+ * done.  @done is HOST memory, nsocks entries, reusable when the call returns
+ * (what xfg_classify_socks_frags wrote); NULL: every record is live.  Socket
+ * s's records i >= done[s] are live for nothing: they go to no ring, are
+ * counted nowhere, and their verdict bytes are not read.  A live record of a
+ * socket with a TX ring whose verdict is XFG_XDP_PASS becomes that socket's
+ * next TX record: addr and len as received, options = the RX record's options
+ * & XFG_XDP_PKT_CONTD.  Every other live record hands its chunk back: in the
+ * shared fill ring at the rank of the live non-PASS records before it in flat
+ * order, in its socket's own at the rank within its socket.  counts[2s] =
+ * socket s's TX records, counts[2s + 1] = done[s] minus that, and the two
+ * totals likewise.  XFG_EGRESS_SWAP_MACS touches head records only: a socket's
+ * record 0, and record i iff record i - 1 of the same socket has the bit
+ * clear.  flags: XFG_EGRESS_SWAP_MACS, with or without XFG_EGRESS_MULTIBUF
+ * (implied here).  No host synchronisation: classify then egress on one stream
+ * need none between them beyond the classify's own.
+ *
+ * -EINVAL: everything xfg_classify_socks and xfg_socks_egress refuse (but for
+ * XFG_EGRESS_MULTIBUF); fr == NULL, fr->sz below the structure's size,
+ * fr->done == NULL, pkt_of not 4-byte aligned; a flag other than the two;
+ * done[s] > count[s].  -ENODEV on a host-only context, after these checks; no
+ * device pointer is touched before it.  total == 0: the classify launches
+ * nothing, zeroes done[] and counts and changes no statistic; the egress
+ * writes zero counts only.
+ *
+ * Not covered: xfg_capture_descs by whole packet (it captures record by
+ * record, and skips the XFG_VERDICT_NONE records), the host-memory ring
+ * (xfg_classify_xsk_host), the CLI, sockets over different UMEMs.
+ */
+#define XFG_VERDICT_NONE 0xffu        /* verdict byte of a record in no complete packet */
+#define XFG_PKT_NONE     0xffffffffu  /* pkt_of of such a record */
+
+struct xfg_socks_frags {
+	size_t sz;           /* sizeof(struct xfg_socks_frags), for extension */
+	uint32_t *done;      /* HOST, out, nsocks x u32: records of socket s in complete packets
+	                      * (what to xsk_ring_cons__release on that socket) */
+	uint32_t *pkt_of;    /* device, total x u32, 4-byte aligned, or NULL */
+	uint64_t counts[3];  /* HOST, out: packets, records in them (sum of done[]), trailing
+	                      * records (total - that), over all sockets */
+};
+
+int xfg_classify_socks_frags(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+			     struct xfg_socks_frags *fr, uint8_t *verdicts, void *stream);
+
+int xfg_socks_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+			   const struct xfg_socks_egress *e, const uint32_t *done,
+			   const uint8_t *verdicts, void *stream);
 
 /*
  * Capture by verdict: the frames of a device-resident batch that a program

@@ -45,8 +45,15 @@
       socket beside one xfg_classify_socks + one xfg_socks_egress, whole rounds
       by host wall clock (the cost at issue is the calls' own), us a round,
       Mpps and the ratio
+  c3sm  c3m's three-record packets scattered over --socks sockets of --batch
+      records (same defaults and --sweep as c3s), odd sockets' batches ending in
+      the middle of a packet: a poll round as xfg_classify_descs_frags +
+      xfg_ring_egress(MULTIBUF) a socket beside one xfg_classify_socks_frags +
+      one xfg_socks_frags_egress, first checked to produce the same rings; whole
+      rounds by host wall clock (at least five runs a leg), each leg's classify
+      and egress calls alone, and the ratio
 
-  c1 xdpfilt_alw_eth, the 8 MAC rules 02:00:00:00:00:0{1..8} (4 dst, 4
+  c1xdpfilt_alw_eth, the 8 MAC rules 02:00:00:00:00:0{1..8} (4 dst, 4
       src), 64 B Ethernet/IPv4/UDP frames, 25% carrying a ruled MAC (SURVEY.md
       §8d: BASELINE.json configs[0], the reference's in-kernel CPU case): the
       GPU path, and the CPU restatement timed on the same batch on 1 thread
@@ -619,10 +626,188 @@ def run_c3s(args):
     f.close()
 
 
+def run_c3sm(args):
+    """c3m's three-record packets scattered over S sockets of B records: every
+    socket's batch is packets of a head and two continuation chunks from its
+    record 0 on; B is no multiple of 3, so the last record of an even socket is
+    a packet of its own and that of an odd socket the head of a packet the
+    batch ends in the middle of.  The round as the per-ring calls make it --
+    xfg_classify_descs_frags (a host synchronisation each) and
+    xfg_ring_egress(MULTIBUF) a socket -- beside one xfg_classify_socks_frags
+    and one xfg_socks_frags_egress; first both are checked to produce the same
+    rings.  Whole rounds by host wall clock as c3s times them, then each leg's
+    classify calls and egress calls alone (the per-step split)."""
+    import ctypes as C
+    import statistics
+    import numpy as np
+    import xfgpu as G
+    points = ([(s, b) for b in (64, 256) for s in (4, 64, 1024)] if args.sweep
+              else [(args.socks, args.batch)])
+    most = max(s * b for s, b in points)
+    w = c3d_workload(args, "c3sm", umem_chunks=3, log2_default=max(12, (most - 1).bit_length()),
+                     descs_min_packets=0)
+    f, nf, stride = w.f, w.n, w.stride
+    assert most <= nf, "more records than --log2-packets frames"
+    # continuation chunk nf + k holds a frame that hits a rule (as c3m's do)
+    f.classify_descs(w.d_umem.ptr, w.d_descs.ptr, nf, w.d_verd.ptr, first=w.first, mask=w.entries - 1)
+    f.sync()
+    hv = w.d_verd.download(np.zeros(nf, np.uint8))
+    hit = np.flatnonzero(hv == 2)[:4096]          # (deny program: a hit passes)
+    assert len(hit) >= 16, "no frames that hit a rule"
+    which = hit[np.random.default_rng(14).integers(0, len(hit), most)]
+    buf = np.zeros((most, C3D_CHUNK), np.uint8)
+    buf[:, C3D_HEADROOM:C3D_HEADROOM + stride] = w.data.reshape(nf, stride)[which]
+    G._check(G.lib.xfg_memcpy_h2d(f.ctx, 0, w.d_umem.ptr + nf * C3D_CHUNK, buf.ctypes.data,
+                                  buf.nbytes), "memcpy_h2d")
+    del buf
+    CONTD = np.uint64(G.XDP_PKT_CONTD << 32)
+    lib, ctx = G.lib, f.ctx
+    for S, B in points:
+        n, R = S * B, 2 * B                    # every ring twice the batch, wrapping inside it
+        first = R - 7
+        j = np.arange(B)
+        s_of = np.repeat(np.arange(S), B)
+        head = np.tile(j % 3 == 0, S)
+        # a record continues its packet unless it is the packet's third, or an
+        # even socket's last record
+        cont = np.tile(j % 3 != 2, S) & ~(np.tile(j == B - 1, S) & (s_of % 2 == 0))
+        nh, nc = int(head.sum()), int((~head).sum())
+        rec = np.zeros((n, 2), np.uint64)
+        rec[head, 0] = w.perm[:nh].astype(np.uint64) * np.uint64(C3D_CHUNK) + np.uint64(C3D_HEADROOM)
+        rec[head, 1] = w.lens[:nh].astype(np.uint64)
+        rec[~head, 0] = (nf + np.arange(nc)).astype(np.uint64) * np.uint64(C3D_CHUNK) + np.uint64(C3D_HEADROOM)
+        rec[~head, 1] = w.lens[which[:nc]].astype(np.uint64)
+        rec[cont, 1] |= CONTD
+        descs = np.zeros((S, R, 2), np.uint64)
+        descs[:, (first + j) & (R - 1)] = rec.reshape(S, B, 2)
+        d_rx = f.alloc(descs.nbytes)
+        d_rx.upload(descs)
+        d_tx, d_fill = [f.alloc(16 * S * R) for _ in range(2)], [f.alloc(8 * S * R) for _ in range(2)]
+        d_v = [f.alloc(n), f.alloc(n)]
+        d_c = [f.alloc(16 * S), f.alloc(8 * (2 * S + 2))]
+        for d in d_tx + d_fill:
+            d.upload(np.zeros(d.nbytes, np.uint8))
+
+        def rings(k):
+            return [dict(rx_descs=d_rx.ptr + 16 * R * s, rx_first=first, rx_mask=R - 1,
+                         tx_descs=d_tx[k].ptr + 16 * R * s, tx_first=R - 5, tx_mask=R - 1,
+                         fill_addrs=d_fill[k].ptr + 8 * R * s, fill_first=R - 3, fill_mask=R - 1, count=B)
+                    for s in range(S)]
+
+        # leg 1: the structures of every call built once, the library called directly
+        per = []
+        for s, r in enumerate(rings(0)):
+            db = G.DescBatch(w.d_umem.ptr, r["rx_descs"], first, R - 1, B)
+            fr = G.Frags(C.sizeof(G.Frags), None)
+            e = G.Egress(C.sizeof(G.Egress), None, r["rx_descs"], first, R - 1, r["tx_descs"],
+                         r["tx_first"], R - 1, r["fill_addrs"], r["fill_first"], R - 1, 0,
+                         d_c[0].ptr + 16 * s, G.EGRESS_MULTIBUF)
+            per.append((C.byref(db), fr, e, d_v[0].ptr + s * B, db))
+        tab = G.sock_table(rings(1))
+        sk = G.Socks(C.sizeof(G.Socks), w.d_umem.ptr, tab, None, S)
+        done = (C.c_uint32 * S)()
+        sfr = G.SocksFrags(C.sizeof(G.SocksFrags), done, None)
+        se = G.SocksEgress(C.sizeof(G.SocksEgress), None, 0, 0, d_c[1].ptr, 0)
+
+        def loop_classify():
+            for db, fr, e, v, _ in per:
+                rc = lib.xfg_classify_descs_frags(ctx, 0, db, C.byref(fr), v, None)
+                assert rc == 0, rc
+                e.count = fr.counts[1]             # frags_done: what the egress takes
+
+        def loop_egress():
+            for _, _, e, v, _ in per:
+                rc = lib.xfg_ring_egress(ctx, 0, C.byref(e), v, None)
+                assert rc == 0, rc
+
+        def loop_round():
+            for db, fr, e, v, _ in per:
+                rc = lib.xfg_classify_descs_frags(ctx, 0, db, C.byref(fr), v, None)
+                e.count = fr.counts[1]
+                rc = rc or lib.xfg_ring_egress(ctx, 0, C.byref(e), v, None)
+                assert rc == 0, rc
+
+        def single_classify():
+            rc = lib.xfg_classify_socks_frags(ctx, 0, C.byref(sk), C.byref(sfr), d_v[1].ptr, None)
+            assert rc == 0, rc
+
+        def single_egress():
+            rc = lib.xfg_socks_frags_egress(ctx, 0, C.byref(sk), C.byref(se), done, d_v[1].ptr, None)
+            assert rc == 0, rc
+
+        def single_round():
+            single_classify()
+            single_egress()
+
+        # both legs make the same round: verdicts of the live records, done[],
+        # every ring whole, every count
+        loop_round()
+        single_round()
+        f.sync()
+        want_done = np.where(np.arange(S) % 2 == 0, B, B - B % 3 if B % 3 else B)
+        got_done = np.frombuffer(done, np.uint32)
+        assert np.array_equal(got_done, want_done), "done[] differs"
+        assert np.array_equal(got_done, [int(p[1].counts[1]) for p in per])
+        assert tuple(sfr.counts) == (sum(int(p[1].counts[0]) for p in per), int(got_done.sum()),
+                                     n - int(got_done.sum()))
+        live = np.tile(j, S) < np.repeat(got_done.astype(np.int64), B)
+        v0, v1 = (d.download(np.zeros(n, np.uint8)) for d in d_v)
+        assert np.array_equal(v0[live], v1[live]) and np.all(v1[~live] == G.VERDICT_NONE)
+        for pair in (d_tx, d_fill):
+            r0, r1 = (d.download(np.zeros(d.nbytes, np.uint8)) for d in pair)
+            assert r0.any() and np.array_equal(r0, r1), "the rings differ"
+        c0 = d_c[0].download(np.zeros(2 * S, np.uint64))
+        c1 = d_c[1].download(np.zeros(2 * S + 2, np.uint64))
+        assert np.array_equal(c0, c1[:2 * S]) and int(c1[2 * S]) == int(np.count_nonzero(v1 == 2))
+        legs = {"per_socket_loop": loop_round, "single_call": single_round}
+        steps = {"per_socket_loop_classify": loop_classify, "per_socket_loop_egress": loop_egress,
+                 "single_call_classify": single_classify, "single_call_egress": single_egress}
+        timed = dict(legs, **steps)
+        rounds, us, paths = {}, {k: [] for k in timed}, {}
+        for k, one in timed.items():                # warm-up, and how many rounds a run needs
+            for _ in range(3):
+                one()
+            f.sync()
+            t0 = time.perf_counter()
+            for _ in range(3):
+                one()
+            f.sync()
+            rounds[k] = int(min(2000, max(5, 0.1 / ((time.perf_counter() - t0) / 3))))
+            paths[k] = f.last_path()
+        for _ in range(max(5, args.runs)):
+            for k, one in timed.items():
+                t0 = time.perf_counter()
+                for _ in range(rounds[k]):
+                    one()
+                f.sync()
+                us[k].append((time.perf_counter() - t0) / rounds[k] * 1e6)
+        line = {"config": "c3sm", "program": f.prog_name, "socks": S, "batch": B, "records": n,
+                "packets": int(sfr.counts[0]), "records_in_packets": int(sfr.counts[1]),
+                "trailing_records": int(sfr.counts[2]), "rules_ipv4": w.n4, "port_rules": w.nports,
+                "pass_records": int(c1[2 * S]),
+                "calls_per_round": {"per_socket_loop": 2 * S, "single_call": 2},
+                "host_syncs_per_round": {"per_socket_loop": S, "single_call": 1}}
+        for k in legs:
+            med = statistics.median(us[k])
+            line[k] = {"us_per_round": [round(u, 1) for u in us[k]], "median_us": round(med, 1),
+                       "Mrecords_per_s": round(n / med, 2), "rounds_per_run": rounds[k],
+                       "spread": round((max(us[k]) - min(us[k])) / med, 3), "kernel_path": paths[k]}
+        line["steps_median_us"] = {k: round(statistics.median(us[k]), 1) for k in steps}
+        line["ratio"] = round(line["per_socket_loop"]["median_us"] / line["single_call"]["median_us"], 2)
+        # faster by more than the runs of either leg differ among themselves
+        line["single_call_faster_beyond_spread"] = bool(max(us["single_call"]) < min(us["per_socket_loop"]))
+        print(json.dumps(line), flush=True)
+        for b in [d_rx] + d_tx + d_fill + d_v + d_c:
+            b.free()
+    f.close()
+
+
 def run(name, args):
     import numpy as np
     import xftools as X
     import xfgpu as G
+    if name == "c3sm":
+        return run_c3sm(args)
     if name == "c3s":
         return run_c3s(args)
     if name == "c1":
@@ -731,11 +916,11 @@ def main():
     ap.add_argument("--no-host", action="store_true",
                     help="c5: the device-resident leg only (PMC passes of its kernel)")
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--socks", type=int, default=64, help="c3s: sockets a round")
+    ap.add_argument("--socks", type=int, default=64, help="c3s, c3sm: sockets a round")
     ap.add_argument("--batch", type=int, default=64,
-                    help="c3s: records peeked from each socket (a power of two)")
+                    help="c3s, c3sm: records peeked from each socket (a power of two)")
     ap.add_argument("--sweep", action="store_true",
-                    help="c3s: sockets 4, 64, 1024 x batch 64, 256 instead of one point")
+                    help="c3s, c3sm: sockets 4, 64, 1024 x batch 64, 256 instead of one point")
     a = ap.parse_args()
     for c in a.configs:
         run(c, a)

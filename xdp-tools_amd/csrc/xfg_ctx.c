@@ -48,6 +48,11 @@ int xfg_launch_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *
 			    uint32_t done, unsigned grid, void *stream);
 int xfg_launch_socks_gather(const struct xfg_socks_gather_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_egress(const struct xfg_socks_kargs *a, unsigned grid, void *stream);
+int xfg_launch_socks_frags_heads(const struct xfg_socks_frags_kargs *a, unsigned grid, void *stream);
+int xfg_launch_socks_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *verdicts,
+				  uint32_t n, unsigned grid, void *stream);
+int xfg_launch_socks_frags_egress(const struct xfg_socks_frags_egress_kargs *a, unsigned grid,
+				  void *stream);
 int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 		       unsigned long long *hits, uint32_t n, void *stream);
 
@@ -62,7 +67,7 @@ int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 /* many sockets (xfg_classify_socks, xfg_socks_egress): socket tables on their
  * way to the device at one time; a slot holds the largest table */
 #define SOCKS_SLOTS 8
-#define SOCKS_SLOT_BYTES ((XFG_SOCKS_TABLE_BYTES(XFG_SOCKS_MAX) + 63) & ~63ull)
+#define SOCKS_SLOT_BYTES ((XFG_SOCKS_FRAGS_TABLE_BYTES(XFG_SOCKS_MAX) + 63) & ~63ull)
 _Static_assert(XFG_SOCKS_MAX == XFG_SOCKS_TABLE_MAX, "the kernels' table of bases");
 
 struct dev_map {           /* device arrays of one hash map */
@@ -176,6 +181,10 @@ struct xfg_dev {
 	uint32_t sk_next;
 	void *sk_flat;
 	uint64_t sk_flat_bytes;
+	/* xfg_classify_socks_frags (under frags_lock, whose scratch it shares):
+	 * pinned room for its one read-back, the state words from the gave-up
+	 * word to the end of done[] */
+	unsigned long long *sf_got;
 	hipEvent_t ev_user, ev_done;    /* ordering against a caller's stream */
 };
 
@@ -494,6 +503,7 @@ static void dev_free(struct xfg_dev *d)
 			hipEventDestroy(d->sk_done[k]);
 	}
 	hipFree(d->sk_flat);
+	hipHostFree(d->sf_got);
 	if (d->ev_user)
 		hipEventDestroy(d->ev_user);
 	if (d->ev_done)
@@ -2239,9 +2249,13 @@ static int socks_check(const struct xfg_socks *sk, uint64_t *total)
  * current): into the next staging slot -- waiting for the slot's last user,
  * SOCKS_SLOTS calls ago, only if that is still in flight -- and from there to
  * the slot's device copy on the device's stream.  The caller launches the
- * kernel that reads it and then calls socks_table_done(). */
+ * kernel that reads it and then calls socks_table_done().  With @live
+ * (xfg_socks_frags_egress) the table carries, behind the bases, the sockets'
+ * live records -- @done[s], or every record where @done is NULL -- and their
+ * prefix sums (xfg_layout.h): live[0] and live[1] their device addresses. */
 static int socks_table(struct xfg_dev *d, const struct xfg_socks *sk, int *slot,
-		       const struct xfg_sock_ent **ents, const uint32_t **base)
+		       const struct xfg_sock_ent **ents, const uint32_t **base,
+		       const uint32_t *done, const uint32_t **live)
 {
 	int err = 0;
 	const int k = (int)d->sk_next;
@@ -2264,12 +2278,28 @@ static int socks_table(struct xfg_dev *d, const struct xfg_socks *sk, int *slot,
 		n += q->count;
 	}
 	hb[sk->nsocks] = n;
-	HIPCHK(hipMemcpyAsync(d->sk_dev[k], d->sk_host[k], XFG_SOCKS_TABLE_BYTES(sk->nsocks),
+	if (live) {
+		uint32_t *hd = hb + sk->nsocks + 1, *hp = hd + sk->nsocks;
+		n = 0;
+		for (uint32_t s = 0; s < sk->nsocks; s++) {
+			hd[s] = done ? done[s] : sk->socks[s].count;
+			hp[s] = n;
+			n += hd[s];
+		}
+		hp[sk->nsocks] = n;
+	}
+	HIPCHK(hipMemcpyAsync(d->sk_dev[k], d->sk_host[k],
+			      live ? XFG_SOCKS_FRAGS_TABLE_BYTES(sk->nsocks)
+				   : XFG_SOCKS_TABLE_BYTES(sk->nsocks),
 			      hipMemcpyHostToDevice, d->stream));
 	d->sk_next = (uint32_t)(k + 1) % SOCKS_SLOTS;
 	*slot = k;
 	*ents = (const struct xfg_sock_ent *)d->sk_dev[k];
 	*base = (const uint32_t *)(*ents + sk->nsocks);
+	if (live) {
+		live[0] = *base + sk->nsocks + 1;
+		live[1] = live[0] + sk->nsocks;
+	}
 fail:
 	return err;
 }
@@ -2315,7 +2345,7 @@ int xfg_classify_socks(xfg_ctx *ctx, int dev, const struct xfg_socks *sk, uint8_
 	if ((err = stream_enter(d, stream)))
 		goto fail;
 	entered = 1;
-	if ((err = socks_table(d, sk, &slot, &a.ents, &a.base)))
+	if ((err = socks_table(d, sk, &slot, &a.ents, &a.base, NULL, NULL)))
 		goto fail;
 	err = xfg_launch_socks_gather(&a, (unsigned)d->ncu * 8, d->stream);
 	const int e1 = socks_table_done(d, slot);
@@ -2338,20 +2368,13 @@ fail:
 	return err;
 }
 
-/* Every socket's TX ring and the fill ring(s) in one launch: like
- * xfg_ring_egress on the device's own stream between the two events, over the
- * same status buffer. */
-int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
-		     const struct xfg_socks_egress *e, const uint8_t *verdicts, void *stream)
+/* What both egress calls check beyond socks_check(): @flags_ok the flags the
+ * call takes. */
+static int socks_egress_check(const struct xfg_socks *sk, const struct xfg_socks_egress *e,
+			      const uint8_t *verdicts, uint64_t total, uint32_t flags_ok)
 {
-	uint64_t total = 0;
-	int err, slot = -1;
-	if (!ctx)
-		return -EINVAL;
-	if ((err = socks_check(sk, &total)))
-		return err;
 	if (!e || e->sz < sizeof(*e) || !e->counts || ((uintptr_t)e->counts & 7) ||
-	    (e->flags & ~XFG_EGRESS_SWAP_MACS) || ((uintptr_t)sk->umem & 7) ||
+	    (e->flags & ~flags_ok) || ((uintptr_t)sk->umem & 7) ||
 	    ((e->flags & XFG_EGRESS_SWAP_MACS) && !sk->umem))
 		return -EINVAL;
 	if (e->fill_addrs && (((uintptr_t)e->fill_addrs & 7) || !mask_ok(e->fill_mask) ||
@@ -2367,6 +2390,22 @@ int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 		     (uint64_t)k->fill_mask + 1 < k->count))
 			return -EINVAL;
 	}
+	return 0;
+}
+
+/* Every socket's TX ring and the fill ring(s) in one launch: like
+ * xfg_ring_egress on the device's own stream between the two events, over the
+ * same status buffer. */
+int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+		     const struct xfg_socks_egress *e, const uint8_t *verdicts, void *stream)
+{
+	uint64_t total = 0;
+	int err, slot = -1;
+	if (!ctx)
+		return -EINVAL;
+	if ((err = socks_check(sk, &total)) ||
+	    (err = socks_egress_check(sk, e, verdicts, total, XFG_EGRESS_SWAP_MACS)))
+		return err;
 	if (!ctx->ndev)
 		return -ENODEV;
 	if (dev < 0 || dev >= ctx->ndev)
@@ -2392,9 +2431,169 @@ int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 	};
 	if ((err = stream_enter(d, stream)))
 		goto fail;
-	if (!(err = socks_table(d, sk, &slot, &a.ents, &a.base))) {
+	if (!(err = socks_table(d, sk, &slot, &a.ents, &a.base, NULL, NULL))) {
 		/* (four workgroups a CU: all of them resident) */
 		err = xfg_launch_socks_egress(&a, (unsigned)d->ncu * 4, d->stream);
+		const int e1 = socks_table_done(d, slot);
+		err = err ? err : e1;
+	}
+	/* (also after an error: the caller's stream behind what was queued) */
+	const int e2 = stream_leave(d, stream);
+	err = err ? err : e2;
+fail:
+	pthread_mutex_unlock(&d->lock);
+	return err;
+}
+
+/* Multi-buffer batches of many sockets (include/xdpfilter_gpu.h): the done
+ * pass and the head pass over all the sockets' records, the state words with
+ * done[] and the packet count read back (the call's one host synchronisation,
+ * as in frags_run()), the complete packets' heads classified as a plain
+ * descriptor array through classify(), and the verdicts spread over all the
+ * records.  All of it on the device's own stream, after @stream's earlier work
+ * and before its later.  The head, verdict and packet-index scratch is
+ * frags_run()'s, so frags_lock keeps a second caller of either off it between
+ * the steps (d->lock itself is released for classify(), which takes it). */
+int xfg_classify_socks_frags(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+			     struct xfg_socks_frags *fr, uint8_t *verdicts, void *stream)
+{
+	uint64_t total = 0;
+	int err, entered = 0, slot = -1;
+	if (!ctx)
+		return -EINVAL;
+	if ((err = socks_check(sk, &total)))
+		return err;
+	if (((uintptr_t)sk->flat & 15) || (total && (!sk->umem || !verdicts)))
+		return -EINVAL;
+	if (!fr || fr->sz < sizeof(*fr) || !fr->done || ((uintptr_t)fr->pkt_of & 3))
+		return -EINVAL;
+	if (!ctx->ndev)
+		return -ENODEV;
+	if (dev < 0 || dev >= ctx->ndev)
+		return -EINVAL;
+	memset(fr->done, 0, (size_t)sk->nsocks * 4);
+	fr->counts[0] = fr->counts[1] = fr->counts[2] = 0;
+	if (!total)
+		return 0;
+	struct xfg_dev *d = &ctx->dev[dev];
+	/* the read-back: state words 1 .. 3 and done[] behind them */
+	const uint64_t ngot = XFG_SOCKS_FRAGS_DONE_WORD - 1 + XFG_SOCKS_FRAGS_DONE_WORDS(sk->nsocks);
+	uint64_t packets = 0, recs = 0;
+	pthread_mutex_lock(&d->frags_lock);
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!d->sf_got)
+		HIPCHK(hipHostMalloc((void **)&d->sf_got,
+				     (XFG_SOCKS_FRAGS_DONE_WORD + XFG_SOCKS_FRAGS_DONE_WORDS(XFG_SOCKS_MAX)) * 8,
+				     hipHostMallocDefault));
+	if ((err = cstatus_room(d, XFG_SOCKS_FRAGS_STATE_WORDS(total, sk->nsocks))) ||
+	    (err = scratch(d, &d->fr_heads, &d->fr_heads_bytes, total * 16)) ||
+	    (err = scratch(d, (void **)&d->fr_pv, &d->fr_pv_bytes, total)) ||
+	    (!fr->pkt_of && (err = scratch(d, (void **)&d->fr_pkt, &d->fr_pkt_bytes, total * 4))))
+		goto fail;
+	uint32_t *pkt_of = fr->pkt_of ? fr->pkt_of : d->fr_pkt;
+	struct xfg_socks_frags_kargs a = {
+		.flat = sk->flat, .pkt_of = pkt_of, .heads = d->fr_heads, .state = d->cstatus,
+		.n = (uint32_t)total, .nsocks = sk->nsocks,
+	};
+	if ((err = stream_enter(d, stream)))
+		goto fail;
+	entered = 1;
+	if ((err = socks_table(d, sk, &slot, &a.ents, &a.base, NULL, NULL)))
+		goto fail;
+	/* (four workgroups a CU: all of them resident) */
+	err = xfg_launch_socks_frags_heads(&a, (unsigned)d->ncu * 4, d->stream);
+	const int e1 = socks_table_done(d, slot);
+	if ((err = err ? err : e1))
+		goto fail;
+	HIPCHK(hipMemcpyAsync(d->sf_got, d->cstatus + 1, ngot * 8, hipMemcpyDeviceToHost, d->stream));
+	HIPCHK(hipStreamSynchronize(d->stream));
+	const uint32_t *got_done = (const uint32_t *)(d->sf_got + XFG_SOCKS_FRAGS_DONE_WORD - 1);
+	packets = d->sf_got[1];
+	for (uint32_t s = 0; s < sk->nsocks; s++) {
+		if (got_done[s] > sk->socks[s].count)
+			d->sf_got[0] = 1;
+		recs += got_done[s];
+	}
+	/* (word 1: a look-back gave up) */
+	if (d->sf_got[0] || packets > recs || (packets != 0) != (recs != 0)) {
+		err = -EIO;
+		goto fail;
+	}
+	memcpy(fr->done, got_done, (size_t)sk->nsocks * 4);
+	fr->counts[0] = packets;
+	fr->counts[1] = recs;
+	fr->counts[2] = total - recs;
+	pthread_mutex_unlock(&d->lock);
+	if (packets) {
+		const struct xfg_desc_batch hb = { sk->umem, d->fr_heads, 0, 0xffffffffu, packets };
+		err = classify(ctx, dev, NULL, &hb, d->fr_pv, NULL, 1, NULL);
+	}
+	pthread_mutex_lock(&d->lock);
+	if (hipSetDevice(d->ordinal) != hipSuccess)
+		err = err ? err : -EIO;
+	if (!err)
+		err = xfg_launch_socks_frags_spread(d->fr_pv, pkt_of, verdicts, (uint32_t)total,
+						    (unsigned)d->ncu * 8, d->stream);
+fail:
+	/* (also after an error: the caller's stream behind what was queued) */
+	if (entered) {
+		const int e2 = stream_leave(d, stream);
+		err = err ? err : e2;
+	}
+	pthread_mutex_unlock(&d->lock);
+	pthread_mutex_unlock(&d->frags_lock);
+	return err;
+}
+
+/* ... and their egress: xfg_socks_egress with the sockets' done[] and its
+ * prefix sums shipped behind the bases in the same staging slot. */
+int xfg_socks_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+			   const struct xfg_socks_egress *e, const uint32_t *done,
+			   const uint8_t *verdicts, void *stream)
+{
+	uint64_t total = 0;
+	int err, slot = -1;
+	if (!ctx)
+		return -EINVAL;
+	if ((err = socks_check(sk, &total)) ||
+	    (err = socks_egress_check(sk, e, verdicts, total,
+				      XFG_EGRESS_SWAP_MACS | XFG_EGRESS_MULTIBUF)))
+		return err;
+	for (uint32_t s = 0; done && s < sk->nsocks; s++)
+		if (done[s] > sk->socks[s].count)
+			return -EINVAL;
+	if (!ctx->ndev)
+		return -ENODEV;
+	if (dev < 0 || dev >= ctx->ndev)
+		return -EINVAL;
+	struct xfg_dev *d = &ctx->dev[dev];
+	hipStream_t user = (hipStream_t)stream;
+	const uint32_t *live[2] = { NULL, NULL };
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!total) {   /* no scratch: on the caller's stream itself */
+		HIPCHK(hipMemsetAsync(e->counts, 0, (2 * (size_t)sk->nsocks + 2) * 8,
+				      user ? user : d->stream));
+		goto fail;
+	}
+	if ((err = cstatus_room(d, XFG_SOCKS_STATE_WORDS(total, sk->nsocks))))
+		goto fail;
+	struct xfg_socks_frags_egress_kargs a = {
+		.umem = (e->flags & XFG_EGRESS_SWAP_MACS) ? (uint8_t *)(uintptr_t)sk->umem : NULL,
+		.fill = e->fill_addrs, .verdicts = verdicts,
+		.counts = (unsigned long long *)e->counts, .state = d->cstatus,
+		.fill_first = e->fill_first, .fill_mask = e->fill_mask,
+		.n = (uint32_t)total, .nsocks = sk->nsocks,
+		.swap_macs = !!(e->flags & XFG_EGRESS_SWAP_MACS),
+	};
+	if ((err = stream_enter(d, stream)))
+		goto fail;
+	if (!(err = socks_table(d, sk, &slot, &a.ents, &a.base, done, live))) {
+		a.done = live[0];
+		a.dbase = live[1];
+		/* (four workgroups a CU: all of them resident) */
+		err = xfg_launch_socks_frags_egress(&a, (unsigned)d->ncu * 4, d->stream);
 		const int e1 = socks_table_done(d, slot);
 		err = err ? err : e1;
 	}

@@ -2236,4 +2236,8 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // scheme with a socket table in the place of one ring
 #include "xfg_socks.hip"
 
+// multi-buffer packets of many sockets: the head pass and the segmented
+// egress with a per-socket count of records in complete packets
+#include "xfg_socks_frags.hip"
+
 #endif   // XFG_PART_COMMON

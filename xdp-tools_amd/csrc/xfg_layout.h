@@ -415,6 +415,63 @@ struct xfg_socks_kargs {
 #define XFG_SOCKS_STATE_WORDS(n, nsocks) ((XFG_SOCKS_TILES(n) + (uint64_t)(nsocks) + 4) & ~1ull)
 #define XFG_SOCKS_SPINS (1u << 24)
 
+/* Multi-buffer packets of many sockets (xfg_socks_frags.hip,
+ * xfg_classify_socks_frags() and xfg_socks_frags_egress()).
+ *
+ * Arguments of the done pass and the head pass, which share them: the table,
+ * the flat array the done pass also writes (NULL: none), record i's flat
+ * packet index pkt_of[i] (end-of-packet records before flat record i, or
+ * XFG_PKT_NONE outside a complete packet), the complete packets' head records
+ * copied to heads[pkt_of[i]] (room for n), and the launch's state words, zeroed
+ * by the done pass's launch function -- word 0 the head pass's tile ticket,
+ * word 1 set by a look-back that gave up (XFG_SOCKS_SPINS polls), word 2 the
+ * packets (end-of-packet records of all sockets), word 3 unused, from word
+ * XFG_SOCKS_FRAGS_DONE_WORD the nsocks u32 done[s] (socket s's last
+ * end-of-packet record's index + 1, raised by the done pass with atomicMax,
+ * staged in LDS by the head pass; two a word), behind them one status word a
+ * tile.  The host reads words 1 .. the end of done[] back in one copy. */
+struct xfg_socks_frags_kargs {
+	const struct xfg_sock_ent *ents;
+	const uint32_t *base;
+	void *flat;                     /* 16-byte aligned, n records, or NULL */
+	uint32_t *pkt_of;
+	void *heads;
+	unsigned long long *state;
+	uint32_t n;                     /* records of all sockets, >= 1 */
+	uint32_t nsocks;
+};
+#define XFG_SOCKS_FRAGS_DONE_WORD 4u
+#define XFG_SOCKS_FRAGS_DONE_WORDS(nsocks) (((uint64_t)(nsocks) + 1) / 2)
+#define XFG_SOCKS_FRAGS_STATE_WORDS(n, nsocks) \
+	((XFG_SOCKS_FRAGS_DONE_WORD + XFG_SOCKS_FRAGS_DONE_WORDS(nsocks) + XFG_SOCKS_TILES(n) + 1) & ~1ull)
+#define XFG_SOCKS_FRAGS_VERDICT_NONE 0xffu       /* XFG_VERDICT_NONE */
+#define XFG_SOCKS_FRAGS_PKT_NONE 0xffffffffu     /* XFG_PKT_NONE */
+
+/* Arguments of the segmented egress kernel over multi-buffer batches: those of
+ * struct xfg_socks_kargs and, shipped behind the bases in the same table, the
+ * nsocks done[s] (socket s's records i < done[s] are live, the others go
+ * nowhere) and the nsocks + 1 dbase[s] (the live records of the sockets before
+ * s: the prefix sums of done[], dbase[nsocks] their total).  The state words
+ * are laid out as XFG_SOCKS_STATE_WORDS' (a socket's word: PASS records before
+ * base[s]). */
+struct xfg_socks_frags_egress_kargs {
+	uint8_t *umem;                  /* written only with swap_macs */
+	const struct xfg_sock_ent *ents;
+	const uint32_t *base;
+	const uint32_t *done;
+	const uint32_t *dbase;
+	uint64_t *fill;
+	const uint8_t *verdicts;
+	unsigned long long *counts;     /* 2 * nsocks + 2 */
+	unsigned long long *state;
+	uint32_t fill_first, fill_mask;
+	uint32_t n;                     /* records of all sockets, >= 1 */
+	uint32_t nsocks;
+	uint32_t swap_macs;
+};
+#define XFG_SOCKS_FRAGS_TABLE_BYTES(nsocks) \
+	(XFG_SOCKS_TABLE_BYTES(nsocks) + (2 * (uint64_t)(nsocks) + 1) * 4)
+
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 #define XFG_HD __host__ __device__ __forceinline__

@@ -51,8 +51,8 @@
 // XFG_EGRESS_SWAP_MACS: as in xfg_egress.hip, for the records that count as
 // PASS.
 //
-// Not here: multi-buffer packets (their sockets keep xfg_classify_descs_frags
-// and xfg_ring_egress), sockets over different UMEMs.
+// Not here: multi-buffer packets (xfg_socks_frags.hip, which reuses this
+// file's table, search and waits), sockets over different UMEMs.
 
 namespace {
 constexpr int SK_LANES = 256;

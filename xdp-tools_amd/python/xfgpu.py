@@ -64,8 +64,11 @@ EXPORTS = [
     "xfg_host_unregister", "xfg_last_path", "xfg_host_threads", "xfg_classify_descs_timed",
     "xfg_ring_egress", "xfg_capture", "xfg_capture_descs", "xfg_classify_descs_frags",
     "xfg_classify_descs_frags_timed", "xfg_classify_socks", "xfg_socks_egress",
+    "xfg_classify_socks_frags", "xfg_socks_frags_egress",
 ]
 SOCKS_MAX = 1024
+VERDICT_NONE = 0xff          # XFG_VERDICT_NONE
+PKT_NONE = 0xffffffff        # XFG_PKT_NONE
 EGRESS_SWAP_MACS = 1
 EGRESS_MULTIBUF = 4
 XDP_PKT_CONTD = 1
@@ -133,6 +136,12 @@ class SocksEgress(C.Structure):
     """struct xfg_socks_egress (xfg_socks_egress)."""
     _fields_ = [("sz", C.c_size_t), ("fill_addrs", C.c_void_p), ("fill_first", C.c_uint32),
                 ("fill_mask", C.c_uint32), ("counts", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class SocksFrags(C.Structure):
+    """struct xfg_socks_frags (xfg_classify_socks_frags)."""
+    _fields_ = [("sz", C.c_size_t), ("done", C.POINTER(C.c_uint32)), ("pkt_of", C.c_void_p),
+                ("counts", C.c_uint64 * 3)]
 
 
 def sock_table(socks):
@@ -221,7 +230,12 @@ def _load():
         "xfg_classify_socks": (C.c_int, [vp, C.c_int, C.POINTER(Socks), vp, vp]),
         "xfg_socks_egress": (C.c_int, [vp, C.c_int, C.POINTER(Socks), C.POINTER(SocksEgress), vp,
                                        vp]),
-        "xfg_capture": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.POINTER(Capture), vp]),
+        "xfg_classify_socks_frags": (C.c_int, [vp, C.c_int, C.POINTER(Socks),
+                                               C.POINTER(SocksFrags), vp, vp]),
+        "xfg_socks_frags_egress": (C.c_int, [vp, C.c_int, C.POINTER(Socks),
+                                             C.POINTER(SocksEgress), C.POINTER(C.c_uint32), vp,
+                                             vp]),
+        "xfg_capture":(C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.POINTER(Capture), vp]),
         "xfg_capture_descs": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp, C.POINTER(Capture),
                                         vp]),
         "xfg_classify_timed": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.c_int,
@@ -634,6 +648,38 @@ class Filter:
         e = SocksEgress(C.sizeof(SocksEgress), fill_ptr, fill_first, fill_mask, counts_ptr, flags)
         _check(lib.xfg_socks_egress(self.ctx, dev, C.byref(sk), C.byref(e), verdicts_ptr, stream),
                "socks_egress")
+
+    def classify_socks_frags(self, umem_ptr, socks, verdicts_ptr, nsocks=None, pkt_of_ptr=None,
+                             flat_ptr=None, dev=0, stream=None):
+        """One classify for the multi-buffer RX batches of many sockets over
+        one UMEM (xfg_classify_socks_frags): a verdict byte per record in flat
+        order, VERDICT_NONE for a socket's trailing incomplete packet.
+        Returns (done, counts): done[s] the records of socket s in complete
+        packets (u32 array), counts (packets, records in them, trailing)."""
+        tab = socks if isinstance(socks, C.Array) else sock_table(socks)
+        ns = len(socks) if nsocks is None else nsocks
+        sk = Socks(C.sizeof(Socks), umem_ptr, tab, flat_ptr, ns)
+        done = np.zeros(max(ns, 1), np.uint32)
+        fr = SocksFrags(C.sizeof(SocksFrags), done.ctypes.data_as(C.POINTER(C.c_uint32)), pkt_of_ptr)
+        _check(lib.xfg_classify_socks_frags(self.ctx, dev, C.byref(sk), C.byref(fr), verdicts_ptr,
+                                            stream), "classify_socks_frags")
+        return done[:ns], tuple(int(c) for c in fr.counts)
+
+    def socks_frags_egress(self, socks, verdicts_ptr, counts_ptr, done=None, nsocks=None,
+                           fill_ptr=None, fill_first=0, fill_mask=0xffffffff, umem_ptr=None,
+                           flags=0, dev=0, stream=None):
+        """xfg_socks_egress for multi-buffer batches (xfg_socks_frags_egress):
+        done[s] records of socket s are live (None: all), a TX record keeps
+        XDP_PKT_CONTD; counts_ptr: 2 * nsocks + 2 u64 on the device."""
+        tab = socks if isinstance(socks, C.Array) else sock_table(socks)
+        sk = Socks(C.sizeof(Socks), umem_ptr, tab, None, len(socks) if nsocks is None else nsocks)
+        e = SocksEgress(C.sizeof(SocksEgress), fill_ptr, fill_first, fill_mask, counts_ptr, flags)
+        d = None
+        if done is not None:
+            done = np.ascontiguousarray(done, np.uint32)
+            d = done.ctypes.data_as(C.POINTER(C.c_uint32))
+        _check(lib.xfg_socks_frags_egress(self.ctx, dev, C.byref(sk), C.byref(e), d, verdicts_ptr,
+                                          stream), "socks_frags_egress")
 
     def capture_into(self, batch, verdicts_ptr, action_mask, out_ptr, out_bytes, counts_ptr,
                      snaplen=0, ts_ns_ptr=None, ts0=0, dev=0, stream=None):
