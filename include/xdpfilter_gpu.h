@@ -282,9 +282,10 @@ int xfg_classify_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch
  * end-of-packet record in the batch: {0, 0, count}, nothing classified, no
  * stats change, verdicts untouched.
  *
- * Not covered: xfg_capture_descs of multi-buffer packets (it keeps capturing
- * record by record, each record's bytes under its packet's verdict),
- * xfg_classify_xsk_host, and the CLI.
+ * Capture by whole packet: xfg_capture_descs_frags with count = counts[1]
+ * (xfg_capture_descs keeps capturing record by record, each record's bytes
+ * under its packet's verdict).  Not covered: xfg_classify_xsk_host, and the
+ * CLI.
  */
 #define XFG_XDP_PKT_CONTD (1u << 0)          /* headers/linux/if_xdp.h:123 */
 
@@ -643,9 +644,12 @@ int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
  * nothing, zeroes done[] and counts and changes no statistic; the egress
  * writes zero counts only.
  *
- * Not covered: xfg_capture_descs by whole packet (it captures record by
- * record, and skips the XFG_VERDICT_NONE records), the host-memory ring
- * (xfg_classify_xsk_host), the CLI, sockets over different UMEMs.
+ * Capture by whole packet: xfg_capture_descs_frags over sk->flat with the
+ * call's verdicts; the XFG_VERDICT_NONE bytes keep a socket's trailing records
+ * and the next socket's head apart (xfg_capture_descs captures record by
+ * record, and skips the XFG_VERDICT_NONE records).  Not covered: the
+ * host-memory ring (xfg_classify_xsk_host), the CLI, sockets over different
+ * UMEMs.
  */
 #define XFG_VERDICT_NONE 0xffu        /* verdict byte of a record in no complete packet */
 #define XFG_PKT_NONE     0xffffffffu  /* pkt_of of such a record */
@@ -707,8 +711,9 @@ int xfg_socks_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
  * Stream-ordered on @stream (NULL: the library's stream of the device), as
  * xfg_compact and xfg_ring_egress are: after a classify call on the same
  * stream it needs no host synchronisation.  The call changes no map, counter
- * or statistic.  Single-buffer descriptors only: a multi-buffer packet's
- * records (xfg_classify_descs_frags) are captured record by record.
+ * or statistic.  These two calls take every record as a frame of its own: a
+ * multi-buffer packet's records (xfg_classify_descs_frags) are captured whole
+ * by xfg_capture_descs_frags below.
  */
 struct xfg_capture {
 	size_t sz;              /* sizeof(struct xfg_capture), for extension */
@@ -725,6 +730,57 @@ int xfg_capture(xfg_ctx *ctx, int dev, const struct xfg_batch *batch, const uint
 		const struct xfg_capture *cap, void *stream);
 int xfg_capture_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
 		      const uint8_t *verdicts, const struct xfg_capture *cap, void *stream);
+
+/*
+ * Capture by verdict of multi-buffer packets: one block a packet, its
+ * records' bytes concatenated.  @batch, @verdicts and @cap are those of
+ * xfg_capture_descs (array or wrapping ring, the unaligned-chunk address
+ * form, the alignment and read-past rules), and the call serves the output of
+ * both multi-buffer classify calls: xfg_classify_descs_frags with count =
+ * counts[1], and xfg_classify_socks_frags with sk->flat as a plain array
+ * (mask 0xffffffff) of count = total records, whose XFG_VERDICT_NONE bytes
+ * mark the records in no complete packet.
+ *
+ * Packets.  With o[i] record i's options, v[i] its verdict byte and n the
+ * count: live[i] = v[i] != XFG_VERDICT_NONE; eop[i] = !(o[i] &
+ * XFG_XDP_PKT_CONTD); head[i] = live[i] && (i == 0 || !live[i-1] ||
+ * eop[i-1]).  The packet of head h is records h..e, e the smallest index >= h
+ * with eop[e]; it exists only if every record h..e is live and e < n.  A run
+ * of live records that ends -- at the end of the batch or at a record that is
+ * not live -- without an end-of-packet record is no packet: nothing is
+ * captured or counted for it.  A packet is selected by its head's verdict
+ * byte alone (v[h] < 32 and bit v[h] of action_mask); the bytes of its other
+ * records matter only for liveness, and other option bits are ignored.
+ *
+ * The block of a selected packet is the one xfg_pcapng_write_captured()
+ * writes for a frame whose bytes are the records' bytes in order, total =
+ * len[h] + ... + len[e] of them: cap = snaplen ? min(total, snaplen) : total,
+ * L = 52 + ((cap + 3) & ~3), header dwords 5 and 6 cap and total, the verdict
+ * v[h], the timestamp ts_ns[h] (ts_ns stays one entry per record) or ts0, pad
+ * bytes zero.  With XFG_CAPTURE_HEAD_ONLY packets are formed the same way but
+ * the frame is the head record alone, total = len[h]: what xdpdump sees of a
+ * multi-buffer frame (pkt_len = data_end - data, xdp-dump/xdpdump_bpf.c:76-77,
+ * xdpdump_xdp.c:51-52).  Placement, overflow and the three counts are as for
+ * xfg_capture, over packets.  If every record is an end-of-packet record and
+ * no verdict byte is XFG_VERDICT_NONE, output and counts are those of
+ * xfg_capture_descs.
+ *
+ * count < 2^32; a packet's lengths sum below 2^25 - 64; its record count is
+ * not limited, and the cost does not grow with it.  Two kernels on the
+ * device's stream (a segmented scan over the records, then the copy) and
+ * 12 bytes a record of library scratch, grown on demand.  Stream-ordered on
+ * @stream with no host synchronisation; no map, counter or statistic changes.
+ *
+ * -EINVAL: everything xfg_capture_descs refuses, and any flag bit other than
+ * XFG_CAPTURE_HEAD_ONLY.  -ENODEV on a host-only context, after the argument
+ * checks; no device pointer is touched before it.  count == 0 or action_mask
+ * == 0 writes three zero counts and nothing else.
+ */
+#define XFG_CAPTURE_HEAD_ONLY (1u << 0)
+
+int xfg_capture_descs_frags(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
+			    const uint8_t *verdicts, const struct xfg_capture *cap,
+			    uint32_t flags, void *stream);
 
 /* Per-action stats summed over devices (the userspace per-CPU sum of
  * lib/util/stats.c:140-172), or for one device. */

@@ -39,6 +39,12 @@
       the whole call (wall clock to its return, and to the stream's end), the
       egress with XFG_EGRESS_MULTIBUF timed as c3f's legs are, and c3d
       (xfg_classify_descs_timed) on the same heads for comparison
+  c3mc c3m's batch classified by xfg_classify_descs_frags, then its DROP packets
+      captured whole as pcapng blocks (xfg_capture_descs_frags, snaplen 0), and
+      head only; beside them xfg_capture_descs over the same records and
+      verdicts (the same payload bytes, three times the blocks) -- timed as
+      c3c's legs are, with the bytes moved and their share of the
+      streaming-read rate
   c3s  C3's rules and frames in c3d's UMEM, scattered over --socks sockets of
       --batch records (64 x 64 by default; --sweep: 4, 64, 1024 sockets x 64,
       256 records): a poll round as xfg_classify_descs + xfg_ring_egress a
@@ -393,12 +399,13 @@ def run_c3c(args):
     print(json.dumps(line), flush=True)
 
 
-def run_c3m(args):
-    """c3d's frames as the heads of 3-record packets (see the module text)."""
+def c3m_workload(args, name):
+    """c3m's batch on the device, classified once by xfg_classify_descs_frags
+    and checked against c3d's verdicts of the heads (shared by c3m and c3mc)."""
+    import types
     import numpy as np
-    import torch
     import xfgpu as G
-    w = c3d_workload(args, "c3m", umem_chunks=3)
+    w = c3d_workload(args, name, umem_chunks=3)
     f, n, stride = w.f, w.n, w.stride
     t0 = time.time()
     # c3d on the heads alone, and their verdicts: the frames that hit a rule
@@ -440,7 +447,7 @@ def run_c3m(args):
     d_descs, d_verd, d_pkt = f.alloc(descs.nbytes), f.alloc(nrec), f.alloc(4 * nrec)
     d_descs.upload(descs)
     del descs, rec, buf
-    print(f"[c3m] continuations set up {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
+    print(f"[{name}] continuations set up {time.time() - t0:.1f}s", file=sys.stderr, flush=True)
     fa = (w.d_umem.ptr, d_descs.ptr, nrec, d_verd.ptr)
     fk = dict(pkt_of_ptr=d_pkt.ptr, first=first, mask=entries - 1)
     f.stats_reset()
@@ -453,6 +460,106 @@ def run_c3m(args):
     st = f.stats()
     assert int(st[:, 0].sum()) == n, st
     frags_path = f.last_path()
+    return types.SimpleNamespace(w=w, t0=t0, runs=runs, c3d_ms=c3d_ms, c3d_path=c3d_path, hv=hv,
+                                 nrec=nrec, entries=entries, first=first, d_descs=d_descs,
+                                 d_verd=d_verd, d_pkt=d_pkt, fa=fa, fk=fk, v=v,
+                                 frags_path=frags_path)
+
+
+def run_c3mc(args):
+    """c3m's batch classified by xfg_classify_descs_frags, then its DROP
+    packets captured whole (xfg_capture_descs_frags, snaplen 0), head only,
+    and, over the same records and verdicts, record by record
+    (xfg_capture_descs: the same payload bytes in three times the blocks).
+    Each leg is args.iters launches between two events on a caller stream."""
+    import numpy as np
+    import torch
+    import xfgpu as G
+    cm = c3m_workload(args, "c3mc")
+    w, nrec, entries, first, v = cm.w, cm.nrec, cm.entries, cm.first, cm.v
+    f, n = w.f, w.n
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    descs = cm.d_descs.download(np.zeros((entries, 2), np.uint64))
+    lens = (descs[(first + np.arange(nrec)) & (entries - 1), 1] & np.uint64(0xffffffff)) \
+        .astype(np.int64).reshape(n, 3)
+    del descs
+    drop = v[:, 0] == 1
+    ndrop = int(np.count_nonzero(drop))
+    payload = int(lens[drop].sum())
+    total = int((52 + ((lens[drop].sum(axis=1) + 3) & ~3)).sum())
+    total_head = int((52 + ((lens[drop, 0] + 3) & ~3)).sum())
+    total_recs = int((52 + ((lens[drop] + 3) & ~3)).sum())
+    room = max(total, total_recs, 16)
+    d_out, d_c = f.alloc(room), f.alloc(32)
+    b = G.DescBatch(w.d_umem.ptr, cm.d_descs.ptr, first, entries - 1, nrec)
+    legs = {"capture_frags": lambda: f.capture_frags_into(b, cm.d_verd.ptr, 1 << 1, d_out.ptr, room,
+                                                          d_c.ptr, stream=sp),
+            "capture_frags_head_only": lambda: f.capture_frags_into(
+                b, cm.d_verd.ptr, 1 << 1, d_out.ptr, room, d_c.ptr, flags=G.CAPTURE_HEAD_ONLY,
+                stream=sp),
+            "capture_descs_same_records": lambda: f.capture_into(b, cm.d_verd.ptr, 1 << 1, d_out.ptr,
+                                                                 room, d_c.ptr, stream=sp)}
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            call()
+        e0.record(stream)
+        for _ in range(args.iters):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    runs = max(1, args.runs)
+    ms = {k: [] for k in legs}
+    got = {}
+    for _ in range(runs):      # the legs interleaved
+        for k, call in legs.items():
+            ms[k].append(timed(call))
+            got[k] = d_c.download(np.zeros(3, np.uint64)).tolist()
+    assert got["capture_frags"] == [ndrop, total, 0], got
+    assert got["capture_frags_head_only"] == [ndrop, total_head, 0], got
+    assert got["capture_descs_same_records"] == [3 * ndrop, total_recs, 0], got
+    probe = min(n * C3D_CHUNK, 1 << 30)
+    f.stream_read_timed(w.d_umem.ptr, probe, 2)
+    read_gbs = probe / (f.stream_read_timed(w.d_umem.ptr, probe, args.iters) * 1e-3) / 1e9
+    # bytes the algorithm moves.  Whole packets: the scan reads a verdict byte
+    # and a 16-byte record a record, writes off[] (4) and, a packet, its head's
+    # slot of tot[] (8) over the launch's fill (8 a record); the copy reads
+    # tot[] (8 a record), a selected head's verdict byte, and for its block the
+    # records (16 each), their off[] (4 each) and the payload, and writes the
+    # block.  Record by record: as c3c states it.
+    moved = {"capture_frags": nrec * (1 + 16 + 4 + 8 + 8) + 8 * n + ndrop * (1 + 3 * 20) +
+             payload + total,
+             "capture_descs_same_records": nrec + 16 * 3 * ndrop + payload + total_recs}
+    line = {"config": "c3mc", "program": f.prog_name, "packets": n, "records": nrec,
+            "drop_packets": ndrop, "payload_bytes": payload, "capture_bytes": total,
+            "capture_bytes_head_only": total_head, "capture_bytes_record_by_record": total_recs,
+            "iters": args.iters, "stream_read_GBps": round(read_gbs, 1),
+            "setup_s": round(w.setup_s + time.time() - cm.t0, 1)}
+    for k in legs:
+        line[k] = {"ms": [round(m, 4) for m in ms[k]]}
+        if k in moved:
+            gbs = moved[k] / (min(ms[k]) * 1e-3) / 1e9
+            line[k].update(bytes=moved[k], GBps=round(gbs, 1),
+                           frac_of_stream_read=round(gbs / read_gbs, 3))
+    line["frags_over_record_by_record"] = round(
+        min(ms["capture_frags"]) / min(ms["capture_descs_same_records"]), 3)
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
+def run_c3m(args):
+    """c3d's frames as the heads of 3-record packets (see the module text)."""
+    import numpy as np
+    import torch
+    import xfgpu as G
+    cm = c3m_workload(args, "c3m")
+    w, t0, runs, c3d_ms, c3d_path, nrec = cm.w, cm.t0, cm.runs, cm.c3d_ms, cm.c3d_path, cm.nrec
+    entries, first, d_descs, d_verd, fa, fk = cm.entries, cm.first, cm.d_descs, cm.d_verd, cm.fa, cm.fk
+    v, frags_path, f, n = cm.v, cm.frags_path, w.f, w.n
     steps = {"head_pass": [], "classify_heads": [], "spread": []}
     wall_return, wall_done = [], []
     for _ in range(runs):
@@ -820,6 +927,8 @@ def run(name, args):
         return run_c3f(args)
     if name == "c3m":
         return run_c3m(args)
+    if name == "c3mc":
+        return run_c3mc(args)
     kind = {"c2": 2, "c3": 3, "c4": 4, "c5": 5, "c3sd": 3, "c3e": 3}[name]
     n = 1 << (args.log2_packets or {"c2": 24, "c3": 24, "c4": 23, "c5": 23, "c3sd": 24, "c3e": 24}[name])
     stride = 64 if kind in (2, 3) else 1536

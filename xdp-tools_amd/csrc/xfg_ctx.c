@@ -43,6 +43,7 @@ int xfg_launch_compact(const uint8_t *verdicts, uint64_t n, uint32_t action, uin
 uint64_t xfg_compact_tiles(uint64_t n);
 int xfg_launch_egress(const struct xfg_egress_kargs *a, unsigned grid, void *stream);
 int xfg_launch_capture(const struct xfg_capture_kargs *a, unsigned grid, void *stream);
+int xfg_launch_capture_frags(const struct xfg_capture_frags_kargs *a, unsigned grid, void *stream);
 int xfg_launch_frags_heads(const struct xfg_frags_kargs *a, unsigned grid, void *stream);
 int xfg_launch_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *verdicts,
 			    uint32_t done, unsigned grid, void *stream);
@@ -167,6 +168,11 @@ struct xfg_dev {
 	uint8_t *fr_pv;
 	uint32_t *fr_pkt;
 	uint64_t fr_heads_bytes, fr_pv_bytes, fr_pkt_bytes;
+	/* capture of multi-buffer packets (xfg_capture_descs_frags): a record's
+	 * bytes of its packet before it, a head's {bytes, records} */
+	uint32_t *cf_off;
+	unsigned long long *cf_tot;
+	uint64_t cf_off_bytes, cf_tot_bytes;
 	/* many sockets (xfg_classify_socks, xfg_socks_egress).  The caller's
 	 * socket table is host memory it may reuse when a call returns, so each
 	 * call copies it (rings and bases, xfg_layout.h) into the next of a ring
@@ -496,6 +502,8 @@ static void dev_free(struct xfg_dev *d)
 	hipFree(d->fr_heads);
 	hipFree(d->fr_pv);
 	hipFree(d->fr_pkt);
+	hipFree(d->cf_off);
+	hipFree(d->cf_tot);
 	for (int k = 0; k < SOCKS_SLOTS; k++) {
 		hipHostFree(d->sk_host[k]);
 		hipFree(d->sk_dev[k]);
@@ -2686,6 +2694,63 @@ int xfg_capture_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
 		.first = db->first, .mask = db->mask, .form = XFG_CAPTURE_F_DESCS,
 	};
 	return capture_launch(ctx, dev, &a, db->count, c, stream);
+}
+
+/* Capture of multi-buffer packets, one block a packet (include/
+ * xdpfilter_gpu.h): capture_launch() with two kernels, two sets of status
+ * words in one request, and the per-record scratch of the scan. */
+int xfg_capture_descs_frags(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+			    const uint8_t *verdicts, const struct xfg_capture *c, uint32_t flags,
+			    void *stream)
+{
+	int err = 0;
+	if (!ctx || !db || !mask_ok(db->mask) || (flags & ~XFG_CAPTURE_HEAD_ONLY))
+		return -EINVAL;
+	if (db->count && !db->descs)
+		return -EINVAL;
+	if (((uintptr_t)db->descs & 7) || ((uintptr_t)db->umem & 15))
+		return -EINVAL;
+	if (!c || c->sz < sizeof(*c) || !c->counts || ((uintptr_t)c->counts & 7) ||
+	    ((uintptr_t)c->ts_ns & 7) || ((uintptr_t)c->out & 15) || (!c->out && c->out_bytes) ||
+	    (!verdicts && db->count) || db->count > 0xffffffffull)
+		return -EINVAL;
+	if (!ctx->ndev)
+		return -ENODEV;
+	if (dev < 0 || dev >= ctx->ndev)
+		return -EINVAL;
+	if (db->count && !db->umem)
+		return -EINVAL;
+	struct xfg_dev *d = &ctx->dev[dev];
+	hipStream_t user = (hipStream_t)stream;
+	const uint64_t n = db->count;
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!n || !c->action_mask) {   /* no scratch: on the caller's stream itself */
+		HIPCHK(hipMemsetAsync(c->counts, 0, 24, user ? user : d->stream));
+		goto fail;
+	}
+	if ((err = cstatus_room(d, XFG_CAPTURE_FRAGS_STATE_WORDS(n))) ||
+	    (err = scratch(d, (void **)&d->cf_off, &d->cf_off_bytes, n * 4)) ||
+	    (err = scratch(d, (void **)&d->cf_tot, &d->cf_tot_bytes, n * 8)))
+		goto fail;
+	struct xfg_capture_frags_kargs a = {
+		.umem = db->umem, .descs = db->descs, .verdicts = verdicts,
+		.ts_ns = c->ts_ns, .ts0 = c->ts0, .out = c->out, .out_bytes = c->out_bytes,
+		.counts = (unsigned long long *)c->counts, .state = d->cstatus,
+		.off = d->cf_off, .tot = d->cf_tot,
+		.n = (uint32_t)n, .first = db->first, .mask = db->mask,
+		.action_mask = c->action_mask, .snaplen = c->snaplen,
+		.head_only = !!(flags & XFG_CAPTURE_HEAD_ONLY),
+	};
+	if ((err = stream_enter(d, stream)))
+		goto fail;
+	/* (four workgroups a CU: all of them resident) */
+	err = xfg_launch_capture_frags(&a, (unsigned)d->ncu * 4, d->stream);
+	if (!err)
+		err = stream_leave(d, stream);
+fail:
+	pthread_mutex_unlock(&d->lock);
+	return err;
 }
 
 /* Achievable streaming-read rate of the device (bench.py roofline leg). */

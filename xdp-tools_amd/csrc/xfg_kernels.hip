@@ -2228,6 +2228,10 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // over bytes
 #include "xfg_capture.hip"
 
+// capture of multi-buffer packets, one block a packet: a segmented scan over
+// the records, then the capture kernel over packets
+#include "xfg_capture_frags.hip"
+
 // multi-buffer AF_XDP packets (head pass, verdict spread): the egress
 // kernel's scheme over the end-of-packet flags
 #include "xfg_frags.hip"

@@ -347,6 +347,34 @@ struct xfg_capture_kargs {
 #define XFG_CAPTURE_TILES(n) (((uint64_t)(n) + XFG_CAPTURE_TILE - 1) / XFG_CAPTURE_TILE)
 #define XFG_CAPTURE_STATE_WORDS(n) ((XFG_CAPTURE_TILES(n) + 3) & ~1ull)
 
+/* Arguments of the two kernels of xfg_capture_descs_frags()
+ * (xfg_capture_frags.hip): the records, their verdict bytes, the selection and
+ * the output as for the capture kernel; off[i] (n x u32, library scratch) the
+ * bytes of record i's packet before it; tot[i] (n x u64, library scratch,
+ * filled with ones by the launch) for the head of a complete packet {bytes,
+ * records << 32}, written by the packet's end-of-packet record.  The state
+ * words are two sets of the capture kernel's, the scan's and then the copy's,
+ * zeroed by the launch function together with the three counts. */
+struct xfg_capture_frags_kargs {
+	const uint8_t *umem;
+	const void *descs;              /* struct xdp_desc records */
+	const uint8_t *verdicts;
+	const uint64_t *ts_ns;          /* NULL: ts0 for every packet */
+	uint64_t ts0;
+	uint8_t *out;
+	uint64_t out_bytes;
+	unsigned long long *counts;     /* {blocks written, their bytes, selected not written} */
+	unsigned long long *state;
+	uint32_t *off;
+	unsigned long long *tot;
+	uint32_t n;                     /* records, >= 1 */
+	uint32_t first, mask;
+	uint32_t action_mask;           /* != 0 */
+	uint32_t snaplen;
+	uint32_t head_only;             /* XFG_CAPTURE_HEAD_ONLY */
+};
+#define XFG_CAPTURE_FRAGS_STATE_WORDS(n) (2 * XFG_CAPTURE_STATE_WORDS(n))
+
 /* Arguments of the head pass over a multi-buffer RX batch (xfg_frags.hip,
  * xfg_classify_descs_frags()): the RX records, record i's packet index
  * pkt_of[i] (end-of-packet records before i), the head records copied to

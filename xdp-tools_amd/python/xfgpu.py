@@ -64,8 +64,9 @@ EXPORTS = [
     "xfg_host_unregister", "xfg_last_path", "xfg_host_threads", "xfg_classify_descs_timed",
     "xfg_ring_egress", "xfg_capture", "xfg_capture_descs", "xfg_classify_descs_frags",
     "xfg_classify_descs_frags_timed", "xfg_classify_socks", "xfg_socks_egress",
-    "xfg_classify_socks_frags", "xfg_socks_frags_egress",
+    "xfg_classify_socks_frags", "xfg_socks_frags_egress", "xfg_capture_descs_frags",
 ]
+CAPTURE_HEAD_ONLY = 1        # XFG_CAPTURE_HEAD_ONLY
 SOCKS_MAX = 1024
 VERDICT_NONE = 0xff          # XFG_VERDICT_NONE
 PKT_NONE = 0xffffffff        # XFG_PKT_NONE
@@ -238,6 +239,8 @@ def _load():
         "xfg_capture":(C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.POINTER(Capture), vp]),
         "xfg_capture_descs": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp, C.POINTER(Capture),
                                         vp]),
+        "xfg_capture_descs_frags": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp,
+                                              C.POINTER(Capture), C.c_uint32, vp]),
         "xfg_classify_timed": (C.c_int, [vp, C.c_int, C.POINTER(Batch), vp, C.c_int,
                                          C.POINTER(C.c_double)]),
         "xfg_classify_descs_timed": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), vp, C.c_int,
@@ -719,6 +722,33 @@ class Filter:
         assert isinstance(batch, DescBatch)
         return self.capture(batch, verdicts, action_mask, snaplen, out_bytes, ts_ns, ts0, dev,
                             stream)
+
+    def capture_frags_into(self, batch, verdicts_ptr, action_mask, out_ptr, out_bytes, counts_ptr,
+                           snaplen=0, ts_ns_ptr=None, ts0=0, flags=0, dev=0, stream=None):
+        """capture_into() of a DescBatch of multi-buffer packets, one block a packet
+        (xfg_capture_descs_frags); flags: CAPTURE_HEAD_ONLY.  Stream-ordered."""
+        assert isinstance(batch, DescBatch)
+        c = Capture(C.sizeof(Capture), action_mask, snaplen, ts_ns_ptr, ts0, out_ptr, out_bytes,
+                    counts_ptr)
+        _check(lib.xfg_capture_descs_frags(self.ctx, dev, C.byref(batch), verdicts_ptr,
+                                           C.byref(c), flags, stream), "capture_descs_frags")
+
+    def capture_descs_frags(self, batch, verdicts, action_mask, snaplen=0, out_bytes=1 << 26,
+                            ts_ns=None, ts0=0, flags=0, dev=0, stream=None):
+        """capture_frags_into() a buffer of out_bytes of its own: (blocks, written, lost) as
+        capture_descs() returns them, over packets."""
+        room = (max(out_bytes, 16) + 15) & ~15
+        d_out, d_c = self.alloc(room, dev), self.alloc(32, dev)
+        try:
+            self.capture_frags_into(batch, verdicts, action_mask, d_out.ptr if out_bytes else None,
+                                    out_bytes, d_c.ptr, snaplen, ts_ns, ts0, flags, dev, stream)
+            self.sync()
+            counts = d_c.download(np.zeros(3, np.uint64))
+            blocks = d_out.download(np.zeros(int(counts[1]), np.uint8))
+        finally:
+            d_out.free()
+            d_c.free()
+        return blocks, int(counts[0]), int(counts[2])
 
     def classify_timed(self, data_ptr, lens_ptr, count, stride, verdicts_ptr, iters,
                        offsets_ptr=None, lens_u16=False, dev=0):
