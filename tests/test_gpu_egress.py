@@ -24,7 +24,8 @@ PASS = 2
 OTHERS = np.array([0, 1, 3, 4, 255], np.uint8)     # every verdict byte but PASS counts as "other"
 ADDR48 = np.uint64(2**48 - 1)
 A5 = np.uint64(0xA5A5A5A5A5A5A5A5)
-SIZES = [0, 1, 63, 64, 65, 255, 256, 257, 4095, 4096, 4097, 3 * 65536 + 7, 2**22 + 13]
+SIZES = [0, 1, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 4095, 4096, 4097, 3 * 2048 + 7,
+         3 * 65536 + 7, 2**22 + 13]
 PATTERNS = ["random", "all_pass", "no_pass", "alternating", "tile_last"]
 
 

@@ -253,7 +253,7 @@ def test_cli_removal_algebra_traffic(G, cli, tmp_path, opts, left):
     cli("unload", "veth0")
 
 
-@pytest.mark.parametrize("n", [0, 1, 15, 4095, 4096, 4097, 65536 * 3 + 7, (1 << 22) + 13])
+@pytest.mark.parametrize("n", [0, 1, 15, 4095, 4096, 4097, 3 * 4096 + 7, 65536 * 3 + 7, (1 << 22) + 13])
 def test_compact_matches_nonzero(G, n):
     """Ordered verdict compaction (xfg_compact) equals np.nonzero for every
     action, on tile-boundary and ragged sizes."""

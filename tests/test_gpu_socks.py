@@ -45,13 +45,18 @@ def layouts():
         "empties": (0, 5, 0, 0, 64, 0),
         "wave_edges": (64,) * 64,                        # a boundary on every wave edge
         "in_wave": (1, 1, 2, 3, 57, 1, 63, 64, 65),      # several inside one wave
+        "tile_less": (T - 65, 64),                       # one tile less a record, one tile, ...
+        "tile": (T - 64, 64),
+        "tile_more": (T - 64, 65),                       # ... and a record: the first look-back
         "tile_edges": (T - 1, 1, T, 1, T + 1),           # on and next to tile edges
+        "three_tiles": (2 * T, T + 7),                   # a base across two predecessors
         "carry": (3 * T + 7, 2),                         # one socket across three tiles, one behind it
         "many": tuple(int(c) for c in many),             # the largest table, 0..3 records each
     }
 
 
-LAYOUTS = ["one", "empties", "wave_edges", "in_wave", "tile_edges", "carry", "many"]
+LAYOUTS = ["one", "empties", "wave_edges", "in_wave", "tile_less", "tile", "tile_more", "tile_edges",
+           "three_tiles", "carry", "many"]
 
 
 @pytest.fixture(scope="module")

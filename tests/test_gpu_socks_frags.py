@@ -86,6 +86,11 @@ def layout(name):
         counts = [3 * t + 7]
         c = random_cont(rng, counts[0])
         c[-2:] = 1
+    elif name in ("tile_less", "tile", "tile_more"):
+        # one tile less a record, one tile, and one tile and a record: the first look-back
+        counts = [t - 65, 64 + ("tile_less", "tile", "tile_more").index(name)]
+        c = random_cont(rng, sum(counts))
+        c[-2:] = 1
     elif name == "no_eop":
         counts = [1, 1, 2, 3, 57, 1, 63, 64, 65]
         c = np.ones(sum(counts), np.uint32)
@@ -292,6 +297,10 @@ ROUNDS = {
     "many_ring_own": dict(name="many", kind="ring", shared=False, flat=False),
     "many_array_shared_swap": dict(name="many", kind="array", shared=True, swap=True, stream=True,
                                    no_tx=(5, 6, 7, 500)),
+    # batches that end next to the first tile's edge
+    "tile_less_ring_own": dict(name="tile_less", kind="ring", shared=False),
+    "tile_array_shared": dict(name="tile", kind="array", shared=True, flat=False),
+    "tile_more_ring_shared": dict(name="tile_more", kind="ring", shared=True, stream=True),
     # one socket alone: xfg_classify_descs_frags and xfg_ring_egress themselves
     "one_ring_own": dict(name="one", kind="ring", shared=False),
     "one_ring_shared": dict(name="one", kind="ring", shared=True, flat=False, swap=True),

@@ -15,15 +15,12 @@
 //   then              0x00090007 (option 7, length 9), 2 | v << 8, 0, 0
 //   then              0 (end of options), L
 //
-// One pass in the egress kernel's scheme (xfg_egress.hip), over bytes instead
-// of records: a workgroup takes tiles of XFG_CAPTURE_TILE packets in ticket
-// order; in pass k lane l owns packet tile * T + k * 256 + l.  A wave scan
-// over the L of the selected frames gives a block's start in its wave and
-// pass, an LDS step over the (pass, wave) sums its start in the tile, and a
-// decoupled look-back over the earlier tiles' {flag, bytes} status words (62
-// bits of value) the tile's start in the buffer.  A tile waits only for tiles
-// whose tickets were drawn before its own, by workgroups already running, and
-// the grid is no larger than what is resident, so the look-back cannot starve.
+// One pass in the tile scan's scheme (xfg_scan.hip), over bytes instead of a
+// predicate, tiles of XFG_CAPTURE_TILE packets: a wave scan over the L of the
+// selected frames gives a block's start in its wave and pass, an LDS step
+// over the (pass, wave) sums its start in the tile, and the look-back over
+// the earlier tiles' {flag, bytes} status words (62 bits of value) the tile's
+// start in the buffer.
 //
 // The copy is driven from the output side.  The blocks of a wave's 64 frames
 // of one pass are contiguous in the buffer, so the tile's {start, len, source,
@@ -48,26 +45,16 @@
 // adds its three sums to counts[] once, when the tiles have run out.
 
 namespace {
-constexpr int CP_LANES = 256;
-constexpr int CP_PASSES = 8;
-constexpr int CP_WAVES = CP_LANES / 64;
+constexpr int CP_LANES = SC_LANES;
+constexpr int CP_PASSES = SC_PASSES;
+constexpr int CP_WAVES = SC_WAVES;
 static_assert(CP_LANES * CP_PASSES == XFG_CAPTURE_TILE, "tile shape");
-constexpr uint64_t CP_ADDR = (1ull << 48) - 1;   // XSK_UNALIGNED_BUF_ADDR_MASK
-constexpr unsigned long long CP_AGG = 1ull << 62, CP_INC = 2ull << 62, CP_VAL = (1ull << 62) - 1;
-
-typedef const __attribute__((address_space(1))) uint8_t cp_gu8;
-typedef const __attribute__((address_space(1))) uint16_t cp_gu16;
-typedef const __attribute__((address_space(1))) uint32_t cp_gu32;
-typedef const __attribute__((address_space(1))) uint64_t cp_gu64;
-typedef const __attribute__((address_space(1))) u32x4 cp_gdesc;
-typedef __attribute__((address_space(1))) uint32_t cp_gu32_w;
 constexpr uint64_t CP_SRC = (1ull << 56) - 1;   // a device address; the verdict byte above it
 }  // namespace
 
 __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_kernel(const xfg_capture_kargs a)
 {
 	__shared__ uint32_t s_tot[CP_PASSES * CP_WAVES];
-	__shared__ uint32_t s_tile;
 	__shared__ unsigned long long s_base;
 	__shared__ unsigned long long s_acc[3];
 	// the tile's entries, [pass][wave][lane]: a block's start in its wave and
@@ -90,10 +77,7 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_kernel(const xfg_capt
 	if (tid < 3)
 		s_acc[tid] = 0;
 	for (;;) {
-		if (tid == 0)
-			s_tile = atomicAdd(ticket, 1u);
-		__syncthreads();
-		const uint32_t t = s_tile;
+		const uint32_t t = xfg_tile_ticket(ticket);
 		if (t >= ntiles)
 			break;
 		// (64-bit: the last tile's lanes past the batch may pass 2^32)
@@ -105,7 +89,7 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_kernel(const xfg_capt
 			const uint64_t i = i0 + (uint64_t)k * CP_LANES;
 			v[k] = 0xff;
 			if (i < n)
-				v[k] = *reinterpret_cast<cp_gu8 *>(vd + i);
+				v[k] = *reinterpret_cast<gu8 *>(vd + i);
 		}
 		// length and source of the selected frames only; L, 0 for the others
 #pragma unroll
@@ -117,15 +101,15 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_kernel(const xfg_capt
 			if (v[k] >= 32 || !((a.action_mask >> v[k]) & 1))
 				continue;
 			if (descs) {
-				const u32x4 rec = *reinterpret_cast<cp_gdesc *>(
+				const u32x4 rec = *reinterpret_cast<gu32x4 *>(
 					rx + 16ull * ((a.first + (uint32_t)i) & a.mask));
 				const uint64_t addr = (uint64_t)rec.y << 32 | rec.x;
-				src[k] = fb + (addr & CP_ADDR) + (addr >> 48);
+				src[k] = fb + (addr & XSK_ADDR) + (addr >> 48);
 				len[k] = rec.z;
 			} else {
-				len[k] = len16 ? (uint32_t)*reinterpret_cast<cp_gu16 *>(lens + 2 * i)
-					       : *reinterpret_cast<cp_gu32 *>(lens + 4 * i);
-				src[k] = fb + (offs ? *reinterpret_cast<cp_gu64 *>(offs + 8 * i)
+				len[k] = len16 ? (uint32_t)*reinterpret_cast<gu16 *>(lens + 2 * i)
+					       : *reinterpret_cast<gu32 *>(lens + 4 * i);
+				src[k] = fb + (offs ? *reinterpret_cast<gu64 *>(offs + 8 * i)
 						    : i * a.stride);
 				// (the slot is the frame's buffer, as for the classify kernels)
 				if (!offs && len[k] > a.stride)
@@ -156,34 +140,8 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_kernel(const xfg_capt
 #pragma unroll
 		for (int g = 0; g < CP_PASSES * CP_WAVES; g++)
 			agg += s_tot[g];
-		// decoupled look-back (one lane): publish the aggregate, walk back
-		if (tid == 0) {
-			unsigned long long base = 0;
-			if (t == 0) {
-				__hip_atomic_store(&status[0], CP_INC | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			} else {
-				__hip_atomic_store(&status[t], CP_AGG | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-				for (uint32_t p = t - 1;;) {
-					const unsigned long long w = __hip_atomic_load(
-						&status[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					if (w & CP_INC) {
-						base += w & CP_VAL;
-						break;
-					}
-					if (w & CP_AGG) {
-						base += w & CP_VAL;
-						p--;   // tile 0 always publishes CP_INC
-						continue;
-					}
-					__builtin_amdgcn_s_sleep(1);   // predecessor still counting
-				}
-				__hip_atomic_store(&status[t], CP_INC | (base + agg), __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			}
-			s_base = base;
-		}
+		if (tid == 0)
+			s_base = xfg_lookback<false>(status, t, agg);
 		__syncthreads();
 		const uint64_t base = s_base;
 		uint64_t gb = base;   // the span of this wave and pass starts here
@@ -235,7 +193,7 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_kernel(const xfg_capt
 						const uint64_t i = (uint64_t)t * XFG_CAPTURE_TILE + e0 + j;
 						val = q == 3 ? (uint32_t)(a.ts0 >> 32) : (uint32_t)a.ts0;
 						if (tsp)
-							val = *reinterpret_cast<cp_gu32 *>(tsp + 8 * i +
+							val = *reinterpret_cast<gu32 *>(tsp + 8 * i +
 											   (q == 3 ? 4 : 0));
 					} else if (q == 5)
 						val = c;
@@ -243,7 +201,7 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_kernel(const xfg_capt
 						val = l;
 				} else if (q < 7u + nq) {
 					const uint32_t o = 4u * (q - 7u);
-					val = *reinterpret_cast<cp_gu32 *>((s_src[e0 + j] & CP_SRC) + o);
+					val = *reinterpret_cast<gu32 *>((s_src[e0 + j] & CP_SRC) + o);
 					if (o + 4u > c)   // the last dword of a cap that is no multiple of 4
 						val &= (1u << (8u * (c & 3u))) - 1u;
 				} else {
@@ -255,12 +213,12 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_kernel(const xfg_capt
 					else if (o == 5)
 						val = L;
 				}
-				*reinterpret_cast<cp_gu32_w *>(out + gb + p) = val;
+				*reinterpret_cast<gu32_w *>(out + gb + p) = val;
 			}
 			for (int w = wave; w < CP_WAVES; w++)
 				gb += s_tot[k * CP_WAVES + w];
 		}
-		__syncthreads();   // s_tile / s_tot and the entries reused
+		__syncthreads();   // s_tot, the entries and the ticket's word reused
 	}
 	if (acc_w)
 		atomicAdd(&s_acc[0], (unsigned long long)acc_w);
@@ -276,13 +234,8 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_kernel(const xfg_capt
 extern "C" int xfg_launch_capture(const struct xfg_capture_kargs *a, unsigned grid, void *stream)
 {
 	hipStream_t s = static_cast<hipStream_t>(stream);
-	const uint64_t ntiles = XFG_CAPTURE_TILES(a->n);
-	if (hipMemsetAsync(a->state, 0, XFG_CAPTURE_STATE_WORDS(a->n) * 8, s) != hipSuccess ||
-	    hipMemsetAsync(a->counts, 0, 24, s) != hipSuccess)
+	if (hipMemsetAsync(a->counts, 0, 24, s) != hipSuccess)
 		return -5;
-	if (grid > ntiles)
-		grid = (unsigned)ntiles;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_capture_kernel, dim3(grid), dim3(CP_LANES), 0, s, *a);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
+	return xfg_scan_launch(xfg_capture_kernel, a->state, XFG_CAPTURE_STATE_WORDS(a->n),
+			       XFG_CAPTURE_TILES(a->n), grid, s, *a);
 }

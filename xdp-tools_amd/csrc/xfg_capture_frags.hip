@@ -14,19 +14,19 @@
 // end of the batch, closes nothing.
 //
 // Two kernels on the device's stream, both in the capture kernel's scheme
-// (tiles of XFG_CAPTURE_TILE records in ticket order, in pass k lane l owns
-// record tile * T + k * 256 + l, decoupled look-back over status words, a
-// grid no larger than what is resident).
+// (the tile scan of xfg_scan.hip over tiles of XFG_CAPTURE_TILE records).
 //
 // The scan.  A segmented forward scan over the records' lengths gives record
 // i the bytes of its segment before it, off[i], and its segment's start: a
 // wave scan with the start flags, an LDS step over the (pass, wave)
 // aggregates {has a start, bytes since the last start (or all of them), last
-// start}, and a look-back whose status value is that triple in 62 bits (1 +
-// 32 + 29; a packet is shorter than 2^25 bytes, and the bytes of a run that is
-// no packet may wrap: nothing reads them).  The walk back ends at the first
-// tile with a start in it, whether that tile has finished its own look-back
-// or not, so a packet of many tiles costs a walk over its own tiles only.
+// start}, and a look-back of its own (the operator is not a sum, so it is not
+// xfg_lookback(); the flags and the progress argument are the same) whose
+// status value is that triple in 62 bits (1 + 32 + 29; a packet is shorter
+// than 2^25 bytes, and the bytes of a run that is no packet may wrap: nothing
+// reads them).  The walk back ends at the first tile with a start in it,
+// whether that tile has finished its own look-back or not, so a packet of
+// many tiles costs a walk over its own tiles only.
 // off[i] goes to library scratch; an end-of-packet record stores {off + len,
 // records} into its head's slot of tot[], which the launch filled with ones:
 // a slot still all ones is no head of a complete packet.  No record walks its
@@ -44,13 +44,10 @@
 // XFG_CAPTURE_HEAD_ONLY the frame is the head record alone.
 
 namespace {
-constexpr uint32_t CF_CONTD = 1u;   // XDP_PKT_CONTD, headers/linux/if_xdp.h:123
 constexpr int CF_SUM_BITS = 29;
 constexpr unsigned long long CF_SUM = (1ull << CF_SUM_BITS) - 1;
 constexpr unsigned long long CF_HAS = 1ull << 61;
 constexpr unsigned long long CF_NONE = ~0ull;   // tot[]: no head of a complete packet
-
-typedef __attribute__((address_space(1))) unsigned long long cf_gu64_w;
 
 __device__ inline unsigned long long cf_pack(bool has, uint32_t idx, uint32_t sum)
 {
@@ -70,7 +67,7 @@ __device__ inline uint32_t cf_payload(const xfg_capture_frags_kargs &a, uint32_t
 	for (;;) {
 		for (uint32_t hi = end; hi - lo > 1u;) {
 			const uint32_t mid = lo + ((hi - lo) >> 1);
-			const uint32_t x = *reinterpret_cast<cp_gu32 *>(offp + 4ull * mid);
+			const uint32_t x = *reinterpret_cast<gu32 *>(offp + 4ull * mid);
 			if (x <= o + got) {
 				lo = mid;
 				ro = x;
@@ -78,24 +75,24 @@ __device__ inline uint32_t cf_payload(const xfg_capture_frags_kargs &a, uint32_t
 				hi = mid;
 			}
 		}
-		const u32x4 rec = *reinterpret_cast<cp_gdesc *>(rx + 16ull * ((a.first + lo) & a.mask));
+		const u32x4 rec = *reinterpret_cast<gu32x4 *>(rx + 16ull * ((a.first + lo) & a.mask));
 		const uint64_t addr = (uint64_t)rec.y << 32 | rec.x;
 		const uint32_t b = o + got - ro;
 		if (b >= rec.z)   // (only past the stated limits)
 			break;
 		const uint32_t take = min(rec.z - b, need - got);
-		const uint64_t p = fb + (addr & CP_ADDR) + (addr >> 48) + b;
+		const uint64_t p = fb + (addr & XSK_ADDR) + (addr >> 48) + b;
 		const uint32_t sh = (uint32_t)p & 3u;
-		uint32_t w = *reinterpret_cast<cp_gu32 *>(p - sh) >> (8u * sh);
+		uint32_t w = *reinterpret_cast<gu32 *>(p - sh) >> (8u * sh);
 		if (take > 4u - sh)
-			w |= *reinterpret_cast<cp_gu32 *>(p - sh + 4u) << (8u * (4u - sh));
+			w |= *reinterpret_cast<gu32 *>(p - sh + 4u) << (8u * (4u - sh));
 		if (take < 4u)
 			w &= (1u << (8u * take)) - 1u;
 		val |= w << (8u * got);
 		got += take;
 		if (got >= need || ++lo >= end)
 			break;
-		ro = *reinterpret_cast<cp_gu32 *>(offp + 4ull * lo);
+		ro = *reinterpret_cast<gu32 *>(offp + 4ull * lo);
 	}
 	return val;
 }
@@ -108,7 +105,7 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_scan_kernel(
 	__shared__ uint32_t s_has[CP_PASSES * CP_WAVES];
 	__shared__ uint32_t s_csum[CP_PASSES * CP_WAVES + 1], s_cidx[CP_PASSES * CP_WAVES + 1];
 	__shared__ uint32_t s_chas[CP_PASSES * CP_WAVES + 1];
-	__shared__ uint32_t s_tile, s_bsum, s_bidx;
+	__shared__ uint32_t s_bsum, s_bidx;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const uint32_t n = a.n;
 	const uint32_t ntiles = (uint32_t)XFG_CAPTURE_TILES(n);
@@ -117,10 +114,7 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_scan_kernel(
 	const uint64_t rx = (uint64_t)(uintptr_t)a.descs, vd = (uint64_t)(uintptr_t)a.verdicts;
 	const uint64_t offp = (uint64_t)(uintptr_t)a.off, totp = (uint64_t)(uintptr_t)a.tot;
 	for (;;) {
-		if (tid == 0)
-			s_tile = atomicAdd(ticket, 1u);
-		__syncthreads();
-		const uint32_t t = s_tile;
+		const uint32_t t = xfg_tile_ticket(ticket);
 		if (t >= ntiles)
 			break;
 		// (64-bit: the last tile's lanes past the batch may pass 2^32)
@@ -136,19 +130,19 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_scan_kernel(
 			len[k] = 0;
 			fl[k] = 0;
 			if (i < n)
-				v = *reinterpret_cast<cp_gu8 *>(vd + i);
+				v = *reinterpret_cast<gu8 *>(vd + i);
 			if (v != 0xff) {
-				const u32x4 rec = *reinterpret_cast<cp_gdesc *>(
+				const u32x4 rec = *reinterpret_cast<gu32x4 *>(
 					rx + 16ull * ((a.first + (uint32_t)i) & a.mask));
 				len[k] = rec.z;
-				fl[k] = 1u | (rec.w & CF_CONTD) << 1;
+				fl[k] = 1u | (rec.w & XSK_CONTD) << 1;
 			}
 			// a wave's lane 0: does record i - 1 continue?
 			if (lane == 0 && i < n && i > 0 &&
-			    *reinterpret_cast<cp_gu8 *>(vd + i - 1) != 0xff)
-				fl[k] |= (*reinterpret_cast<cp_gu32 *>(
+			    *reinterpret_cast<gu8 *>(vd + i - 1) != 0xff)
+				fl[k] |= (*reinterpret_cast<gu32 *>(
 						  rx + 16ull * ((a.first + (uint32_t)i - 1u) & a.mask) + 12) &
-					  CF_CONTD) << 2;
+					  XSK_CONTD) << 2;
 		}
 #pragma unroll
 		for (int k = 0; k < CP_PASSES; k++) {
@@ -216,28 +210,28 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_scan_kernel(
 			const uint32_t rhas = s_chas[CP_PASSES * CP_WAVES];
 			uint32_t bsum = 0, bidx = 0;
 			if (t == 0) {   // (record 0 is a start)
-				__hip_atomic_store(&status[0], CP_INC | cf_pack(true, ridx, rsum),
+				__hip_atomic_store(&status[0], CT_INC | cf_pack(true, ridx, rsum),
 						   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			} else {
-				__hip_atomic_store(&status[t], CP_AGG | cf_pack(rhas, ridx, rsum),
+				__hip_atomic_store(&status[t], CT_AGG | cf_pack(rhas, ridx, rsum),
 						   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 				for (uint32_t p = t - 1;;) {
 					const unsigned long long w = __hip_atomic_load(
 						&status[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					if ((w & CP_INC) || ((w & CP_AGG) && (w & CF_HAS))) {
+					if ((w & CT_INC) || ((w & CT_AGG) && (w & CF_HAS))) {
 						bsum += (uint32_t)(w & CF_SUM);
 						bidx = (uint32_t)(w >> CF_SUM_BITS);
 						break;
 					}
-					if (w & CP_AGG) {
+					if (w & CT_AGG) {
 						bsum += (uint32_t)(w & CF_SUM);
-						p--;   // tile 0 always publishes CP_INC
+						p--;   // tile 0 always publishes CT_INC
 						continue;
 					}
 					__builtin_amdgcn_s_sleep(1);   // predecessor still scanning
 				}
 				__hip_atomic_store(&status[t],
-						   CP_INC | (rhas ? cf_pack(true, ridx, rsum)
+						   CT_INC | (rhas ? cf_pack(true, ridx, rsum)
 								  : cf_pack(true, bidx, bsum + rsum)),
 						   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			}
@@ -257,12 +251,12 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_scan_kernel(
 				o += s_csum[k * CP_WAVES + wave] + (in_tile ? 0u : bsum);
 				h = in_tile ? s_cidx[k * CP_WAVES + wave] : bidx;
 			}
-			*reinterpret_cast<cp_gu32_w *>(offp + 4ull * i) = o;
+			*reinterpret_cast<gu32_w *>(offp + 4ull * i) = o;
 			if ((eop >> k) & 1)
-				*reinterpret_cast<cf_gu64_w *>(totp + 8ull * h) =
+				*reinterpret_cast<gu64_w *>(totp + 8ull * h) =
 					(unsigned long long)((uint32_t)i - h + 1u) << 32 | (o + len[k]);
 		}
-		__syncthreads();   // s_tile and the aggregates reused
+		__syncthreads();   // the aggregates and the ticket's word reused
 	}
 }
 
@@ -270,7 +264,6 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_copy_kernel(
 	const xfg_capture_frags_kargs a)
 {
 	__shared__ uint32_t s_tot[CP_PASSES * CP_WAVES];
-	__shared__ uint32_t s_tile;
 	__shared__ unsigned long long s_base;
 	__shared__ unsigned long long s_acc[3];
 	// the tile's entries, [pass][wave][lane]: a block's start in its wave and
@@ -293,10 +286,7 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_copy_kernel(
 	if (tid < 3)
 		s_acc[tid] = 0;
 	for (;;) {
-		if (tid == 0)
-			s_tile = atomicAdd(ticket, 1u);
-		__syncthreads();
-		const uint32_t t = s_tile;
+		const uint32_t t = xfg_tile_ticket(ticket);
 		if (t >= ntiles)
 			break;
 		// (64-bit: the last tile's lanes past the batch may pass 2^32)
@@ -308,7 +298,7 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_copy_kernel(
 			tw[k] = CF_NONE;
 			if (i < n)
 				tw[k] = __builtin_nontemporal_load(
-					reinterpret_cast<cp_gu64 *>(totp + 8ull * i));
+					reinterpret_cast<gu64 *>(totp + 8ull * i));
 		}
 		// a block's start: in its wave and pass ...
 #pragma unroll
@@ -316,11 +306,11 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_copy_kernel(
 			const uint64_t i = i0 + (uint64_t)k * CP_LANES;
 			uint32_t v = 0xff, len = 0, blen = 0;
 			if (tw[k] != CF_NONE)   // the head of a complete packet
-				v = *reinterpret_cast<cp_gu8 *>(vd + i);
+				v = *reinterpret_cast<gu8 *>(vd + i);
 			if (v < 32 && ((a.action_mask >> v) & 1)) {
 				len = (uint32_t)tw[k];
 				if (a.head_only)
-					len = (*reinterpret_cast<cp_gdesc *>(
+					len = (*reinterpret_cast<gu32x4 *>(
 						       rx + 16ull * ((a.first + (uint32_t)i) & a.mask))).z;
 				const uint32_t cap = snap && len > snap ? snap : len;
 				blen = 52u + ((cap + 3u) & ~3u);
@@ -347,34 +337,8 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_copy_kernel(
 #pragma unroll
 		for (int g = 0; g < CP_PASSES * CP_WAVES; g++)
 			agg += s_tot[g];
-		// decoupled look-back (one lane): publish the aggregate, walk back
-		if (tid == 0) {
-			unsigned long long base = 0;
-			if (t == 0) {
-				__hip_atomic_store(&status[0], CP_INC | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			} else {
-				__hip_atomic_store(&status[t], CP_AGG | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-				for (uint32_t p = t - 1;;) {
-					const unsigned long long w = __hip_atomic_load(
-						&status[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					if (w & CP_INC) {
-						base += w & CP_VAL;
-						break;
-					}
-					if (w & CP_AGG) {
-						base += w & CP_VAL;
-						p--;   // tile 0 always publishes CP_INC
-						continue;
-					}
-					__builtin_amdgcn_s_sleep(1);   // predecessor still counting
-				}
-				__hip_atomic_store(&status[t], CP_INC | (base + agg), __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			}
-			s_base = base;
-		}
+		if (tid == 0)
+			s_base = xfg_lookback<false>(status, t, agg);
 		__syncthreads();
 		const uint64_t base = s_base;
 		uint64_t gb = base;   // the span of this wave and pass starts here
@@ -426,7 +390,7 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_copy_kernel(
 					else if (q == 3 || q == 4) {
 						val = q == 3 ? (uint32_t)(a.ts0 >> 32) : (uint32_t)a.ts0;
 						if (tsp)
-							val = *reinterpret_cast<cp_gu32 *>(tsp + 8ull * h +
+							val = *reinterpret_cast<gu32 *>(tsp + 8ull * h +
 											   (q == 3 ? 4 : 0));
 					} else if (q == 5)
 						val = c;
@@ -444,12 +408,12 @@ __global__ __launch_bounds__(CP_LANES, 4) void xfg_capture_frags_copy_kernel(
 					else if (o == 5)
 						val = L;
 				}
-				*reinterpret_cast<cp_gu32_w *>(out + gb + p) = val;
+				*reinterpret_cast<gu32_w *>(out + gb + p) = val;
 			}
 			for (int w = wave; w < CP_WAVES; w++)
 				gb += s_tot[k * CP_WAVES + w];
 		}
-		__syncthreads();   // s_tile / s_tot and the entries reused
+		__syncthreads();   // s_tot, the entries and the ticket's word reused
 	}
 	if (acc_w)
 		atomicAdd(&s_acc[0], (unsigned long long)acc_w);
@@ -467,16 +431,11 @@ extern "C" int xfg_launch_capture_frags(const struct xfg_capture_frags_kargs *a,
 {
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	const uint64_t ntiles = XFG_CAPTURE_TILES(a->n);
-	if (hipMemsetAsync(a->state, 0, XFG_CAPTURE_FRAGS_STATE_WORDS(a->n) * 8, s) != hipSuccess ||
-	    hipMemsetAsync(a->counts, 0, 24, s) != hipSuccess ||
+	if (hipMemsetAsync(a->counts, 0, 24, s) != hipSuccess ||
 	    hipMemsetAsync(a->tot, 0xff, 8ull * a->n, s) != hipSuccess)
 		return -5;
-	if (grid > ntiles)
-		grid = (unsigned)ntiles;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_capture_frags_scan_kernel, dim3(grid), dim3(CP_LANES), 0, s, *a);
-	if (hipGetLastError() != hipSuccess)
-		return -5;
-	hipLaunchKernelGGL(xfg_capture_frags_copy_kernel, dim3(grid), dim3(CP_LANES), 0, s, *a);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
+	// (both kernels' state words zeroed ahead of the first)
+	const int err = xfg_scan_launch(xfg_capture_frags_scan_kernel, a->state,
+					XFG_CAPTURE_FRAGS_STATE_WORDS(a->n), ntiles, grid, s, *a);
+	return err ? err : xfg_scan_launch(xfg_capture_frags_copy_kernel, a->state, 0, ntiles, grid, s, *a);
 }

@@ -1891,14 +1891,23 @@ out:
 	return err;
 }
 
-static int check_batch(xfg_ctx *ctx, int dev, const struct xfg_batch *b, const void *verdicts)
+/* the device argument of an entry point (@ctx checked) */
+static int dev_check(const xfg_ctx *ctx, int dev)
 {
-	if (!ctx || !b || (!verdicts && b->count))
-		return -EINVAL;
 	if (!ctx->ndev)
 		return -ENODEV;
 	if (dev < 0 || dev >= ctx->ndev)
 		return -EINVAL;
+	return 0;
+}
+
+static int check_batch(xfg_ctx *ctx, int dev, const struct xfg_batch *b, const void *verdicts)
+{
+	if (!ctx || !b || (!verdicts && b->count))
+		return -EINVAL;
+	const int err = dev_check(ctx, dev);
+	if (err)
+		return err;
 	if (b->count && (!b->data || !b->lens))
 		return -EINVAL;
 	if (!b->offsets && b->count && (b->stride == 0 || (b->stride & 15)))
@@ -1913,10 +1922,9 @@ static int check_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db, c
 {
 	if (!ctx || !db || (!verdicts && db->count))
 		return -EINVAL;
-	if (!ctx->ndev)
-		return -ENODEV;
-	if (dev < 0 || dev >= ctx->ndev)
-		return -EINVAL;
+	const int err = dev_check(ctx, dev);
+	if (err)
+		return err;
 	if (!db->count)
 		return 1;
 	if (!db->umem || !db->descs || ((uintptr_t)db->descs & 7) || (db->mask & (db->mask + 1u)))
@@ -2002,10 +2010,10 @@ int xfg_classify_timed(xfg_ctx *ctx, int dev, const struct xfg_batch *b, uint8_t
 }
 
 /* Room for @words status words in the device's tile status buffer (d->lock
- * held, the device current): shared by xfg_compact, xfg_ring_egress and the
- * capture calls, whose
- * launches run one after the other on the device's stream and each zero the
- * words they use first. */
+ * held, the device current): shared by every launch that goes through
+ * scratch_launch(), by frags_run() and by xfg_classify_socks_frags(), which
+ * run one after the other on the device's stream and each zero the words they
+ * use first. */
 static int cstatus_room(struct xfg_dev *d, uint64_t words)
 {
 	int err = 0;
@@ -2021,37 +2029,71 @@ fail:
 	return err;
 }
 
-/* Verdict compaction (include/xdpfilter_gpu.h).  The kernel uses per-device
- * scratch (tile status words, ticket), so it runs on the device's own stream,
- * ordered after and before the caller's stream: two compactions never
- * overlap on one device, whatever streams their callers pass. */
-int xfg_compact(xfg_ctx *ctx, int dev, const uint8_t *verdicts, uint64_t n, uint32_t action,
-		uint32_t *idx, uint64_t *count, void *stream)
+/* One launch over the device's status scratch (@words of it), on the device's
+ * own stream between @stream's earlier and later work: two such launches never
+ * overlap on a device, whatever streams their callers pass.  @launch (d->lock
+ * held, the device current) points its kernel's state words at d->cstatus and
+ * launches on d->stream with four workgroups a CU, all of them resident.  An
+ * empty batch (@zero: the call's counts, @zero_bytes of them) needs no
+ * scratch: the counts are zeroed on the caller's stream itself.  What else
+ * @launch allocates (the compaction ticket, the capture scan's per-record
+ * scratch) it allocates with the stream entered: a failed allocation costs
+ * the caller's stream one event wait.  Once the device's stream was entered
+ * it is left too, also after a failed launch (the caller's stream behind
+ * whatever was queued); the first error is returned. */
+static int scratch_launch(struct xfg_dev *d, void *stream, void *zero, size_t zero_bytes,
+			  uint64_t words, int (*launch)(struct xfg_dev *d, unsigned grid, void *arg),
+			  void *arg)
 {
 	int err = 0;
-	if (!ctx || !count || (n && (!verdicts || !idx)) || action > 255 || n > 0xffffffffull)
-		return -EINVAL;
-	if (!ctx->ndev)
-		return -ENODEV;
-	if (dev < 0 || dev >= ctx->ndev)
-		return -EINVAL;
-	struct xfg_dev *d = &ctx->dev[dev];
-	uint64_t tiles = xfg_compact_tiles(n);
 	pthread_mutex_lock(&d->lock);
 	HIPCHK(hipSetDevice(d->ordinal));
-	if (!d->cticket)
-		HIPCHK(hipMalloc((void **)&d->cticket, 4));
-	if ((err = cstatus_room(d, tiles)))
+	if (zero) {
+		HIPCHK(hipMemsetAsync(zero, 0, zero_bytes, stream ? (hipStream_t)stream : d->stream));
 		goto fail;
-	if ((err = stream_enter(d, stream)))
+	}
+	if ((err = cstatus_room(d, words)) || (err = stream_enter(d, stream)))
 		goto fail;
-	err = xfg_launch_compact(verdicts, n, action, idx, (unsigned long long *)count,
-				 d->cstatus, d->cticket, (unsigned)d->ncu * 4, d->stream);
-	if (!err)
-		err = stream_leave(d, stream);
+	err = launch(d, (unsigned)d->ncu * 4, arg);
+	const int e2 = stream_leave(d, stream);
+	err = err ? err : e2;
 fail:
 	pthread_mutex_unlock(&d->lock);
 	return err;
+}
+
+/* Verdict compaction (include/xdpfilter_gpu.h). */
+struct compact_job {
+	const uint8_t *verdicts;
+	uint64_t n;
+	uint32_t action;
+	uint32_t *idx;
+	uint64_t *count;
+};
+
+static int compact_go(struct xfg_dev *d, unsigned grid, void *arg)
+{
+	const struct compact_job *j = arg;
+	int err = 0;
+	if (!d->cticket)
+		HIPCHK(hipMalloc((void **)&d->cticket, 4));
+	err = xfg_launch_compact(j->verdicts, j->n, j->action, j->idx, (unsigned long long *)j->count,
+				 d->cstatus, d->cticket, grid, d->stream);
+fail:
+	return err;
+}
+
+int xfg_compact(xfg_ctx *ctx, int dev, const uint8_t *verdicts, uint64_t n, uint32_t action,
+		uint32_t *idx, uint64_t *count, void *stream)
+{
+	int err;
+	if (!ctx || !count || (n && (!verdicts || !idx)) || action > 255 || n > 0xffffffffull)
+		return -EINVAL;
+	if ((err = dev_check(ctx, dev)))
+		return err;
+	struct compact_job j = { verdicts, n, action, idx, count };
+	/* (an empty batch too: its count is zeroed by the launch function) */
+	return scratch_launch(&ctx->dev[dev], stream, NULL, 0, xfg_compact_tiles(n), compact_go, &j);
 }
 
 /* a ring mask: 2^k - 1 (0xffffffff: a plain array) */
@@ -2060,13 +2102,18 @@ static int mask_ok(uint32_t mask)
 	return !(mask & (mask + 1u));
 }
 
-/* AF_XDP egress (include/xdpfilter_gpu.h).  Like xfg_compact it runs on the
- * device's own stream between the two events, over the same status buffer:
- * a compaction and an egress, or two of either, never overlap on a device. */
+/* AF_XDP egress (include/xdpfilter_gpu.h). */
+static int egress_go(struct xfg_dev *d, unsigned grid, void *arg)
+{
+	struct xfg_egress_kargs *a = arg;
+	a->state = d->cstatus;
+	return xfg_launch_egress(a, grid, d->stream);
+}
+
 int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uint8_t *verdicts,
 		    void *stream)
 {
-	int err = 0;
+	int err;
 	if (!ctx || !e || e->sz < sizeof(*e) || !e->counts || ((uintptr_t)e->counts & 7) ||
 	    (e->flags & ~(XFG_EGRESS_SWAP_MACS | XFG_EGRESS_MULTIBUF)) || e->count > 0xffffffffull ||
 	    (!e->tx_descs && !e->fill_addrs))
@@ -2083,25 +2130,12 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uin
 		return -EINVAL;
 	if (e->count && (!e->rx_descs || (e->tx_descs && !verdicts)))
 		return -EINVAL;
-	if (!ctx->ndev)
-		return -ENODEV;
-	if (dev < 0 || dev >= ctx->ndev)
-		return -EINVAL;
-	struct xfg_dev *d = &ctx->dev[dev];
-	hipStream_t user = (hipStream_t)stream;
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!e->count) {   /* no scratch: on the caller's stream itself */
-		HIPCHK(hipMemsetAsync(e->counts, 0, 16, user ? user : d->stream));
-		goto fail;
-	}
-	if ((err = cstatus_room(d, XFG_EGRESS_STATE_WORDS(e->count))))
-		goto fail;
+	if ((err = dev_check(ctx, dev)))
+		return err;
 	struct xfg_egress_kargs a = {
 		.umem = (e->flags & XFG_EGRESS_SWAP_MACS) ? e->umem : NULL,
 		.rx = e->rx_descs, .tx = e->tx_descs, .fill = e->fill_addrs,
 		.verdicts = verdicts, .counts = (unsigned long long *)e->counts,
-		.state = d->cstatus,
 		.rx_first = e->rx_first, .rx_mask = e->rx_mask,
 		.tx_first = e->tx_first, .tx_mask = e->tx_mask,
 		.fill_first = e->fill_first, .fill_mask = e->fill_mask,
@@ -2109,15 +2143,8 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uin
 		.swap_macs = !!(e->flags & XFG_EGRESS_SWAP_MACS),
 		.multibuf = !!(e->flags & XFG_EGRESS_MULTIBUF),
 	};
-	if ((err = stream_enter(d, stream)))
-		goto fail;
-	/* (four workgroups a CU: all of them resident) */
-	err = xfg_launch_egress(&a, (unsigned)d->ncu * 4, d->stream);
-	if (!err)
-		err = stream_leave(d, stream);
-fail:
-	pthread_mutex_unlock(&d->lock);
-	return err;
+	return scratch_launch(&ctx->dev[dev], stream, e->count ? NULL : e->counts, 16,
+			      XFG_EGRESS_STATE_WORDS(e->count), egress_go, &a);
 }
 
 /* Multi-buffer descriptor batches (include/xdpfilter_gpu.h): the head pass
@@ -2335,10 +2362,8 @@ int xfg_classify_socks(xfg_ctx *ctx, int dev, const struct xfg_socks *sk, uint8_
 		return err;
 	if (((uintptr_t)sk->flat & 15) || (total && (!sk->umem || !verdicts)))
 		return -EINVAL;
-	if (!ctx->ndev)
-		return -ENODEV;
-	if (dev < 0 || dev >= ctx->ndev)
-		return -EINVAL;
+	if ((err = dev_check(ctx, dev)))
+		return err;
 	if (!total)
 		return 0;
 	struct xfg_dev *d = &ctx->dev[dev];
@@ -2401,56 +2426,84 @@ static int socks_egress_check(const struct xfg_socks *sk, const struct xfg_socks
 	return 0;
 }
 
-/* Every socket's TX ring and the fill ring(s) in one launch: like
- * xfg_ring_egress on the device's own stream between the two events, over the
- * same status buffer. */
-int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
-		     const struct xfg_socks_egress *e, const uint8_t *verdicts, void *stream)
+/* Every socket's TX ring and the fill ring(s) in one launch
+ * (xfg_socks_egress), and the same over multi-buffer batches
+ * (xfg_socks_frags_egress: @frags, with the sockets' @done[] and its prefix
+ * sums shipped behind the bases in the same staging slot; a TX record then
+ * keeps XDP_PKT_CONTD, so XFG_EGRESS_MULTIBUF is a flag it takes). */
+struct socks_egress_job {
+	const struct xfg_socks *sk;
+	const uint32_t *done;
+	int frags;
+	struct xfg_socks_frags_egress_kargs a;
+};
+
+static int socks_egress_go(struct xfg_dev *d, unsigned grid, void *arg)
+{
+	struct socks_egress_job *j = arg;
+	struct xfg_socks_frags_egress_kargs *a = &j->a;
+	const uint32_t *live[2] = { NULL, NULL };
+	int slot = -1;
+	int err = socks_table(d, j->sk, &slot, &a->ents, &a->base, j->done, j->frags ? live : NULL);
+	if (err)
+		return err;
+	if (j->frags) {
+		a->state = d->cstatus;
+		a->done = live[0];
+		a->dbase = live[1];
+		err = xfg_launch_socks_frags_egress(a, grid, d->stream);
+	} else {
+		/* (the two kernels' argument layouts differ, so field by field: a
+		 * field added to struct xfg_socks_kargs is copied here by hand) */
+		const struct xfg_socks_kargs b = {
+			.umem = a->umem, .ents = a->ents, .base = a->base, .fill = a->fill,
+			.verdicts = a->verdicts, .counts = a->counts, .state = d->cstatus,
+			.fill_first = a->fill_first, .fill_mask = a->fill_mask,
+			.n = a->n, .nsocks = a->nsocks, .swap_macs = a->swap_macs,
+		};
+		err = xfg_launch_socks_egress(&b, grid, d->stream);
+	}
+	const int e1 = socks_table_done(d, slot);
+	return err ? err : e1;
+}
+
+static int socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+			const struct xfg_socks_egress *e, const uint32_t *done,
+			const uint8_t *verdicts, void *stream, int frags)
 {
 	uint64_t total = 0;
-	int err, slot = -1;
+	int err;
 	if (!ctx)
 		return -EINVAL;
 	if ((err = socks_check(sk, &total)) ||
-	    (err = socks_egress_check(sk, e, verdicts, total, XFG_EGRESS_SWAP_MACS)))
+	    (err = socks_egress_check(sk, e, verdicts, total,
+				      XFG_EGRESS_SWAP_MACS | (frags ? XFG_EGRESS_MULTIBUF : 0))))
 		return err;
-	if (!ctx->ndev)
-		return -ENODEV;
-	if (dev < 0 || dev >= ctx->ndev)
-		return -EINVAL;
-	struct xfg_dev *d = &ctx->dev[dev];
-	hipStream_t user = (hipStream_t)stream;
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!total) {   /* no scratch: on the caller's stream itself */
-		HIPCHK(hipMemsetAsync(e->counts, 0, (2 * (size_t)sk->nsocks + 2) * 8,
-				      user ? user : d->stream));
-		goto fail;
-	}
-	if ((err = cstatus_room(d, XFG_SOCKS_STATE_WORDS(total, sk->nsocks))))
-		goto fail;
-	struct xfg_socks_kargs a = {
-		.umem = (e->flags & XFG_EGRESS_SWAP_MACS) ? (uint8_t *)(uintptr_t)sk->umem : NULL,
-		.fill = e->fill_addrs, .verdicts = verdicts,
-		.counts = (unsigned long long *)e->counts, .state = d->cstatus,
-		.fill_first = e->fill_first, .fill_mask = e->fill_mask,
-		.n = (uint32_t)total, .nsocks = sk->nsocks,
-		.swap_macs = !!(e->flags & XFG_EGRESS_SWAP_MACS),
+	for (uint32_t s = 0; done && s < sk->nsocks; s++)
+		if (done[s] > sk->socks[s].count)
+			return -EINVAL;
+	if ((err = dev_check(ctx, dev)))
+		return err;
+	struct socks_egress_job j = {
+		.sk = sk, .done = done, .frags = frags,
+		.a = {
+			.umem = (e->flags & XFG_EGRESS_SWAP_MACS) ? (uint8_t *)(uintptr_t)sk->umem : NULL,
+			.fill = e->fill_addrs, .verdicts = verdicts,
+			.counts = (unsigned long long *)e->counts,
+			.fill_first = e->fill_first, .fill_mask = e->fill_mask,
+			.n = (uint32_t)total, .nsocks = sk->nsocks,
+			.swap_macs = !!(e->flags & XFG_EGRESS_SWAP_MACS),
+		},
 	};
-	if ((err = stream_enter(d, stream)))
-		goto fail;
-	if (!(err = socks_table(d, sk, &slot, &a.ents, &a.base, NULL, NULL))) {
-		/* (four workgroups a CU: all of them resident) */
-		err = xfg_launch_socks_egress(&a, (unsigned)d->ncu * 4, d->stream);
-		const int e1 = socks_table_done(d, slot);
-		err = err ? err : e1;
-	}
-	/* (also after an error: the caller's stream behind what was queued) */
-	const int e2 = stream_leave(d, stream);
-	err = err ? err : e2;
-fail:
-	pthread_mutex_unlock(&d->lock);
-	return err;
+	return scratch_launch(&ctx->dev[dev], stream, total ? NULL : e->counts,
+			      (2 * (size_t)sk->nsocks + 2) * 8, XFG_SOCKS_STATE_WORDS(total, sk->nsocks),
+			      socks_egress_go, &j);
+}
+
+int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
+		     const struct xfg_socks_egress *e, const uint8_t *verdicts, void *stream)
+{
+	return socks_egress(ctx, dev, sk, e, NULL, verdicts, stream, 0);
 }
 
 /* Multi-buffer batches of many sockets (include/xdpfilter_gpu.h): the done
@@ -2475,10 +2528,8 @@ int xfg_classify_socks_frags(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 		return -EINVAL;
 	if (!fr || fr->sz < sizeof(*fr) || !fr->done || ((uintptr_t)fr->pkt_of & 3))
 		return -EINVAL;
-	if (!ctx->ndev)
-		return -ENODEV;
-	if (dev < 0 || dev >= ctx->ndev)
-		return -EINVAL;
+	if ((err = dev_check(ctx, dev)))
+		return err;
 	memset(fr->done, 0, (size_t)sk->nsocks * 4);
 	fr->counts[0] = fr->counts[1] = fr->counts[2] = 0;
 	if (!total)
@@ -2554,111 +2605,66 @@ fail:
 	return err;
 }
 
-/* ... and their egress: xfg_socks_egress with the sockets' done[] and its
- * prefix sums shipped behind the bases in the same staging slot. */
+/* ... and their egress */
 int xfg_socks_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 			   const struct xfg_socks_egress *e, const uint32_t *done,
 			   const uint8_t *verdicts, void *stream)
 {
-	uint64_t total = 0;
-	int err, slot = -1;
-	if (!ctx)
-		return -EINVAL;
-	if ((err = socks_check(sk, &total)) ||
-	    (err = socks_egress_check(sk, e, verdicts, total,
-				      XFG_EGRESS_SWAP_MACS | XFG_EGRESS_MULTIBUF)))
-		return err;
-	for (uint32_t s = 0; done && s < sk->nsocks; s++)
-		if (done[s] > sk->socks[s].count)
-			return -EINVAL;
-	if (!ctx->ndev)
-		return -ENODEV;
-	if (dev < 0 || dev >= ctx->ndev)
-		return -EINVAL;
-	struct xfg_dev *d = &ctx->dev[dev];
-	hipStream_t user = (hipStream_t)stream;
-	const uint32_t *live[2] = { NULL, NULL };
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!total) {   /* no scratch: on the caller's stream itself */
-		HIPCHK(hipMemsetAsync(e->counts, 0, (2 * (size_t)sk->nsocks + 2) * 8,
-				      user ? user : d->stream));
-		goto fail;
-	}
-	if ((err = cstatus_room(d, XFG_SOCKS_STATE_WORDS(total, sk->nsocks))))
-		goto fail;
-	struct xfg_socks_frags_egress_kargs a = {
-		.umem = (e->flags & XFG_EGRESS_SWAP_MACS) ? (uint8_t *)(uintptr_t)sk->umem : NULL,
-		.fill = e->fill_addrs, .verdicts = verdicts,
-		.counts = (unsigned long long *)e->counts, .state = d->cstatus,
-		.fill_first = e->fill_first, .fill_mask = e->fill_mask,
-		.n = (uint32_t)total, .nsocks = sk->nsocks,
-		.swap_macs = !!(e->flags & XFG_EGRESS_SWAP_MACS),
-	};
-	if ((err = stream_enter(d, stream)))
-		goto fail;
-	if (!(err = socks_table(d, sk, &slot, &a.ents, &a.base, done, live))) {
-		a.done = live[0];
-		a.dbase = live[1];
-		/* (four workgroups a CU: all of them resident) */
-		err = xfg_launch_socks_frags_egress(&a, (unsigned)d->ncu * 4, d->stream);
-		const int e1 = socks_table_done(d, slot);
-		err = err ? err : e1;
-	}
-	/* (also after an error: the caller's stream behind what was queued) */
-	const int e2 = stream_leave(d, stream);
-	err = err ? err : e2;
-fail:
-	pthread_mutex_unlock(&d->lock);
-	return err;
+	return socks_egress(ctx, dev, sk, e, done, verdicts, stream, 1);
 }
 
-/* Capture by verdict (include/xdpfilter_gpu.h): both entry points fill the
- * kernel's arguments but for the launch's own (state, counts) and come here.
- * Like xfg_ring_egress it runs on the device's own stream between the two
- * events, over the same status buffer. */
+/* Capture by verdict (include/xdpfilter_gpu.h): what every capture call
+ * checks of @c, the device and its batch of @count frames in @base ... */
+static int capture_check(xfg_ctx *ctx, int dev, const struct xfg_capture *c, const void *verdicts,
+			 const void *base, uint64_t count)
+{
+	if (!c || c->sz < sizeof(*c) || !c->counts || ((uintptr_t)c->counts & 7) ||
+	    ((uintptr_t)c->ts_ns & 7) || ((uintptr_t)c->out & 15) || (!c->out && c->out_bytes) ||
+	    (!verdicts && count) || count > 0xffffffffull)
+		return -EINVAL;
+	int err = dev_check(ctx, dev);
+	if (err)
+		return err;
+	return count && !base ? -EINVAL : 0;
+}
+
+/* ... and of a descriptor batch */
+static int capture_descs_check(xfg_ctx *ctx, const struct xfg_desc_batch *db)
+{
+	if (!ctx || !db || !mask_ok(db->mask))
+		return -EINVAL;
+	if (db->count && !db->descs)
+		return -EINVAL;
+	if (((uintptr_t)db->descs & 7) || ((uintptr_t)db->umem & 15))
+		return -EINVAL;
+	return 0;
+}
+
+static int capture_go(struct xfg_dev *d, unsigned grid, void *arg)
+{
+	struct xfg_capture_kargs *a = arg;
+	a->state = d->cstatus;
+	return xfg_launch_capture(a, grid, d->stream);
+}
+
+/* Both single-record entry points fill the kernel's arguments but for the
+ * launch's own and come here; nothing selected counts as an empty batch. */
 static int capture_launch(xfg_ctx *ctx, int dev, struct xfg_capture_kargs *a, uint64_t count,
 			  const struct xfg_capture *c, void *stream)
 {
-	int err = 0;
-	if (!c || c->sz < sizeof(*c) || !c->counts || ((uintptr_t)c->counts & 7) ||
-	    ((uintptr_t)c->ts_ns & 7) || ((uintptr_t)c->out & 15) || (!c->out && c->out_bytes) ||
-	    (!a->verdicts && count) || count > 0xffffffffull)
-		return -EINVAL;
-	if (!ctx->ndev)
-		return -ENODEV;
-	if (dev < 0 || dev >= ctx->ndev)
-		return -EINVAL;
-	if (count && !a->base)
-		return -EINVAL;
-	struct xfg_dev *d = &ctx->dev[dev];
-	hipStream_t user = (hipStream_t)stream;
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!count || !c->action_mask) {   /* no scratch: on the caller's stream itself */
-		HIPCHK(hipMemsetAsync(c->counts, 0, 24, user ? user : d->stream));
-		goto fail;
-	}
-	if ((err = cstatus_room(d, XFG_CAPTURE_STATE_WORDS(count))))
-		goto fail;
+	int err = capture_check(ctx, dev, c, a->verdicts, a->base, count);
+	if (err)
+		return err;
 	a->ts_ns = c->ts_ns;
 	a->ts0 = c->ts0;
 	a->out = c->out;
 	a->out_bytes = c->out_bytes;
 	a->counts = (unsigned long long *)c->counts;
-	a->state = d->cstatus;
 	a->n = (uint32_t)count;
 	a->action_mask = c->action_mask;
 	a->snaplen = c->snaplen;
-	if ((err = stream_enter(d, stream)))
-		goto fail;
-	/* (four workgroups a CU: all of them resident) */
-	err = xfg_launch_capture(a, (unsigned)d->ncu * 4, d->stream);
-	if (!err)
-		err = stream_leave(d, stream);
-fail:
-	pthread_mutex_unlock(&d->lock);
-	return err;
+	return scratch_launch(&ctx->dev[dev], stream, count && c->action_mask ? NULL : c->counts, 24,
+			      XFG_CAPTURE_STATE_WORDS(count), capture_go, a);
 }
 
 int xfg_capture(xfg_ctx *ctx, int dev, const struct xfg_batch *b, const uint8_t *verdicts,
@@ -2683,12 +2689,9 @@ int xfg_capture(xfg_ctx *ctx, int dev, const struct xfg_batch *b, const uint8_t 
 int xfg_capture_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
 		      const uint8_t *verdicts, const struct xfg_capture *c, void *stream)
 {
-	if (!ctx || !db || !mask_ok(db->mask))
-		return -EINVAL;
-	if (db->count && !db->descs)
-		return -EINVAL;
-	if (((uintptr_t)db->descs & 7) || ((uintptr_t)db->umem & 15))
-		return -EINVAL;
+	int err = capture_descs_check(ctx, db);
+	if (err)
+		return err;
 	struct xfg_capture_kargs a = {
 		.base = db->umem, .descs = db->descs, .verdicts = verdicts,
 		.first = db->first, .mask = db->mask, .form = XFG_CAPTURE_F_DESCS,
@@ -2697,60 +2700,40 @@ int xfg_capture_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
 }
 
 /* Capture of multi-buffer packets, one block a packet (include/
- * xdpfilter_gpu.h): capture_launch() with two kernels, two sets of status
- * words in one request, and the per-record scratch of the scan. */
+ * xdpfilter_gpu.h): two kernels, two sets of status words in one request, and
+ * the per-record scratch of the scan. */
+static int capture_frags_go(struct xfg_dev *d, unsigned grid, void *arg)
+{
+	struct xfg_capture_frags_kargs *a = arg;
+	int err;
+	if ((err = scratch(d, (void **)&d->cf_off, &d->cf_off_bytes, (uint64_t)a->n * 4)) ||
+	    (err = scratch(d, (void **)&d->cf_tot, &d->cf_tot_bytes, (uint64_t)a->n * 8)))
+		return err;
+	a->state = d->cstatus;
+	a->off = d->cf_off;
+	a->tot = d->cf_tot;
+	return xfg_launch_capture_frags(a, grid, d->stream);
+}
+
 int xfg_capture_descs_frags(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
 			    const uint8_t *verdicts, const struct xfg_capture *c, uint32_t flags,
 			    void *stream)
 {
-	int err = 0;
-	if (!ctx || !db || !mask_ok(db->mask) || (flags & ~XFG_CAPTURE_HEAD_ONLY))
+	int err = capture_descs_check(ctx, db);
+	if (err || (flags & ~XFG_CAPTURE_HEAD_ONLY))
 		return -EINVAL;
-	if (db->count && !db->descs)
-		return -EINVAL;
-	if (((uintptr_t)db->descs & 7) || ((uintptr_t)db->umem & 15))
-		return -EINVAL;
-	if (!c || c->sz < sizeof(*c) || !c->counts || ((uintptr_t)c->counts & 7) ||
-	    ((uintptr_t)c->ts_ns & 7) || ((uintptr_t)c->out & 15) || (!c->out && c->out_bytes) ||
-	    (!verdicts && db->count) || db->count > 0xffffffffull)
-		return -EINVAL;
-	if (!ctx->ndev)
-		return -ENODEV;
-	if (dev < 0 || dev >= ctx->ndev)
-		return -EINVAL;
-	if (db->count && !db->umem)
-		return -EINVAL;
-	struct xfg_dev *d = &ctx->dev[dev];
-	hipStream_t user = (hipStream_t)stream;
-	const uint64_t n = db->count;
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!n || !c->action_mask) {   /* no scratch: on the caller's stream itself */
-		HIPCHK(hipMemsetAsync(c->counts, 0, 24, user ? user : d->stream));
-		goto fail;
-	}
-	if ((err = cstatus_room(d, XFG_CAPTURE_FRAGS_STATE_WORDS(n))) ||
-	    (err = scratch(d, (void **)&d->cf_off, &d->cf_off_bytes, n * 4)) ||
-	    (err = scratch(d, (void **)&d->cf_tot, &d->cf_tot_bytes, n * 8)))
-		goto fail;
+	if ((err = capture_check(ctx, dev, c, verdicts, db->umem, db->count)))
+		return err;
 	struct xfg_capture_frags_kargs a = {
 		.umem = db->umem, .descs = db->descs, .verdicts = verdicts,
 		.ts_ns = c->ts_ns, .ts0 = c->ts0, .out = c->out, .out_bytes = c->out_bytes,
-		.counts = (unsigned long long *)c->counts, .state = d->cstatus,
-		.off = d->cf_off, .tot = d->cf_tot,
-		.n = (uint32_t)n, .first = db->first, .mask = db->mask,
+		.counts = (unsigned long long *)c->counts,
+		.n = (uint32_t)db->count, .first = db->first, .mask = db->mask,
 		.action_mask = c->action_mask, .snaplen = c->snaplen,
 		.head_only = !!(flags & XFG_CAPTURE_HEAD_ONLY),
 	};
-	if ((err = stream_enter(d, stream)))
-		goto fail;
-	/* (four workgroups a CU: all of them resident) */
-	err = xfg_launch_capture_frags(&a, (unsigned)d->ncu * 4, d->stream);
-	if (!err)
-		err = stream_leave(d, stream);
-fail:
-	pthread_mutex_unlock(&d->lock);
-	return err;
+	return scratch_launch(&ctx->dev[dev], stream, db->count && c->action_mask ? NULL : c->counts,
+			      24, XFG_CAPTURE_FRAGS_STATE_WORDS(db->count), capture_frags_go, &a);
 }
 
 /* Achievable streaming-read rate of the device (bench.py roofline leg). */

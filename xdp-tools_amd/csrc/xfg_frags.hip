@@ -6,20 +6,17 @@
 //
 // A packet is a run of records ending at the first one with XDP_PKT_CONTD
 // clear (IS_EOP_DESC, lib/util/xdpsock.c:70); a program sees its first record
-// only.  The head pass is the egress kernel's scheme (xfg_egress.hip) with
-// eop = !(options & 1) in the place of verdict == PASS: a workgroup takes
-// tiles of XFG_FRAGS_TILE records in ticket order, in pass k lane l owns
-// record tile * T + k * 256 + l, a ballot gives the end-of-packet records
-// before it in its wave and pass, an LDS step those in the tile, a decoupled
-// look-back over the earlier tiles' {flag, sum} status words the tile's base.
-// That exclusive prefix sum is the record's packet index pkt_of[i].  Record i
-// is a head if i == 0 or record i - 1 ends a packet: the neighbouring lane's
-// bit of the same ballot, or for a wave's lane 0 one 4-byte load of record
-// i - 1's options.  A head is copied as it is to heads[pkt_of[i]], so the
-// packets' first records form a plain descriptor array the classify kernels
-// take.  The last tile leaves the packet count (its inclusive sum) in state
-// word 2; every tile with an end-of-packet record raises state word 3 to its
-// last one's index + 1 (l2fwd()'s frags_done, lib/util/xdpsock.c:1539-1542).
+// only.  The head pass is the tile scan (xfg_scan.hip) over tiles of
+// XFG_FRAGS_TILE records with eop = !(options & 1) as the predicate: the
+// exclusive prefix sum of the end-of-packet records is the record's packet
+// index pkt_of[i].  Record i is a head if i == 0 or record i - 1 ends a
+// packet: the neighbouring lane's bit of the same ballot, or for a wave's
+// lane 0 one 4-byte load of record i - 1's options.  A head is copied as it
+// is to heads[pkt_of[i]], so the packets' first records form a plain
+// descriptor array the classify kernels take.  The last tile leaves the
+// packet count (its inclusive sum) in state word 2; every tile with an
+// end-of-packet record raises state word 3 to its last one's index + 1
+// (l2fwd()'s frags_done, lib/util/xdpsock.c:1539-1542).
 //
 // The spread: verdicts[i] = pv[pkt_of[i]] for the records of complete packets,
 // four records a lane (one 16-byte load of packet indices, one 4-byte store),
@@ -27,24 +24,17 @@
 // the last few singly.
 
 namespace {
-constexpr int FR_LANES = 256;
-constexpr int FR_PASSES = 8;
-constexpr int FR_WAVES = FR_LANES / 64;
-static_assert(FR_LANES * FR_PASSES == XFG_FRAGS_TILE, "tile shape");
-constexpr uint32_t FR_CONTD = 1u;   // XDP_PKT_CONTD, headers/linux/if_xdp.h:123
-
-typedef const __attribute__((address_space(1))) uint32_t fr_gu32;
-typedef __attribute__((address_space(1))) uint32_t fr_gu32_w;
-typedef __attribute__((address_space(1))) u32x4 fr_gu32x4_w;
 typedef u32x4 __attribute__((aligned(4))) u32x4_a4;
 typedef const __attribute__((address_space(1))) u32x4_a4 fr_gidx4;
 }  // namespace
 
-__global__ __launch_bounds__(FR_LANES) void xfg_frags_heads_kernel(const xfg_frags_kargs a)
+static_assert(SC_LANES * SC_PASSES == XFG_FRAGS_TILE, "tile shape");
+
+__global__ __launch_bounds__(SC_LANES) void xfg_frags_heads_kernel(const xfg_frags_kargs a)
 {
-	__shared__ uint32_t s_cnt[FR_PASSES * FR_WAVES];
-	__shared__ uint32_t s_tile, s_base;
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	__shared__ uint32_t s_cnt[SC_SLOTS];
+	__shared__ uint32_t s_base;
+	const int tid = threadIdx.x, lane = tid & 63;
 	const uint32_t n = a.n;
 	const uint32_t ntiles = (uint32_t)XFG_FRAGS_TILES(n);
 	uint32_t *ticket = reinterpret_cast<uint32_t *>(a.state);
@@ -52,88 +42,48 @@ __global__ __launch_bounds__(FR_LANES) void xfg_frags_heads_kernel(const xfg_fra
 	const uint64_t rx = (uint64_t)(uintptr_t)a.rx, heads = (uint64_t)(uintptr_t)a.heads;
 	const uint64_t pko = (uint64_t)(uintptr_t)a.pkt_of;
 	for (;;) {
-		if (tid == 0)
-			s_tile = atomicAdd(ticket, 1u);
-		__syncthreads();
-		const uint32_t t = s_tile;
+		const uint32_t t = xfg_tile_ticket(ticket);
 		if (t >= ntiles)
 			break;
 		// (64-bit: the last tile's lanes past the batch may pass 2^32)
 		const uint64_t i0 = (uint64_t)t * XFG_FRAGS_TILE + tid;
-		u32x4 rec[FR_PASSES];
-		uint32_t prev[FR_PASSES];   // a wave's lane 0: the options of record i - 1
+		u32x4 rec[SC_PASSES];
+		uint32_t prev[SC_PASSES];   // a wave's lane 0: the options of record i - 1
 #pragma unroll
-		for (int k = 0; k < FR_PASSES; k++) {
-			const uint64_t i = i0 + (uint64_t)k * FR_LANES;
-			rec[k] = u32x4{ 0, 0, 0, FR_CONTD };   // past the batch: no end of packet
+		for (int k = 0; k < SC_PASSES; k++) {
+			const uint64_t i = i0 + (uint64_t)k * SC_LANES;
+			rec[k] = u32x4{ 0, 0, 0, XSK_CONTD };   // past the batch: no end of packet
 			prev[k] = 0;
 			if (i < n)
 				rec[k] = __builtin_nontemporal_load(reinterpret_cast<gdesc *>(
 					rx + 16ull * ((a.first + (uint32_t)i) & a.mask)));
 			if (lane == 0 && i < n && i > 0)
-				prev[k] = *reinterpret_cast<fr_gu32 *>(
+				prev[k] = *reinterpret_cast<gu32 *>(
 					rx + 16ull * ((a.first + (uint32_t)i - 1u) & a.mask) + 12);
 		}
 		// end-of-packet records before this lane's record of pass k: in its wave ...
-		uint32_t before[FR_PASSES];
+		uint32_t before[SC_PASSES];
 		uint32_t head = 0;      // bit k: the record of pass k starts a packet
 		uint32_t last = 0;      // the wave's last end-of-packet record's index + 1
 #pragma unroll
-		for (int k = 0; k < FR_PASSES; k++) {
-			const uint64_t i = i0 + (uint64_t)k * FR_LANES;
-			const uint64_t b = __ballot(!(rec[k].w & FR_CONTD));
-			before[k] = __builtin_amdgcn_mbcnt_hi(
-				(uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-			const bool h = lane ? (b >> (lane - 1)) & 1 : !(prev[k] & FR_CONTD);
+		for (int k = 0; k < SC_PASSES; k++) {
+			const uint64_t i = i0 + (uint64_t)k * SC_LANES;
+			const uint64_t b = xfg_wave_rank<false>(!(rec[k].w & XSK_CONTD), k, before[k], s_cnt);
+			const bool h = lane ? (b >> (lane - 1)) & 1 : !(prev[k] & XSK_CONTD);
 			head |= (uint32_t)(i < n && h) << k;
 			if (b)   // (its lanes are inside the batch, below 2^32)
-				last = (uint32_t)(i0 - lane + (uint64_t)k * FR_LANES) + 64u -
+				last = (uint32_t)(i0 - lane + (uint64_t)k * SC_LANES) + 64u -
 				       (uint32_t)__builtin_clzll(b);
-			if (lane == 0)
-				s_cnt[k * FR_WAVES + wave] = __builtin_popcountll(b);
 		}
 		__syncthreads();
-		// ... and in the tile (record order: pass, wave, lane)
-		uint32_t agg = 0;
-#pragma unroll
-		for (int k = 0; k < FR_PASSES; k++) {
-#pragma unroll
-			for (int w = 0; w < FR_WAVES; w++) {
-				if (w == wave)
-					before[k] += agg;
-				agg += s_cnt[k * FR_WAVES + w];
-			}
-		}
+		// ... and in the tile
+		const uint32_t agg = xfg_tile_step<false>(before, s_cnt);
 		// the records in complete packets: the wave's last pass with one
 		if (lane == 0 && last)
 			atomicMax(a.state + 3, (unsigned long long)last);
-		// decoupled look-back (one lane): publish the aggregate, walk back
 		// (a tile without an end-of-packet record publishes 0 like any other)
 		if (tid == 0) {
-			unsigned long long base = 0;
-			if (t == 0) {
-				__hip_atomic_store(&status[0], CT_INC | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			} else {
-				__hip_atomic_store(&status[t], CT_AGG | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-				for (uint32_t p = t - 1;;) {
-					const unsigned long long w = __hip_atomic_load(
-						&status[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					if (w & CT_INC) {
-						base += w & CT_VAL;
-						break;
-					}
-					if (w & CT_AGG) {
-						base += w & CT_VAL;
-						p--;   // tile 0 always publishes CT_INC
-						continue;
-					}
-					__builtin_amdgcn_s_sleep(1);   // predecessor still counting
-				}
-				__hip_atomic_store(&status[t], CT_INC | (base + agg), __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			}
+			const unsigned long long base = xfg_lookback<false>(status, t, agg);
 			s_base = (uint32_t)base;   // (<= n < 2^32)
 			if (t == ntiles - 1)
 				a.state[2] = base + agg;
@@ -141,16 +91,16 @@ __global__ __launch_bounds__(FR_LANES) void xfg_frags_heads_kernel(const xfg_fra
 		__syncthreads();
 		const uint32_t base = s_base;
 #pragma unroll
-		for (int k = 0; k < FR_PASSES; k++) {
-			const uint64_t i = i0 + (uint64_t)k * FR_LANES;
+		for (int k = 0; k < SC_PASSES; k++) {
+			const uint64_t i = i0 + (uint64_t)k * SC_LANES;
 			if (i >= n)
 				continue;
 			const uint32_t p = base + before[k];   // end-of-packet records before i: <= i
-			*reinterpret_cast<fr_gu32_w *>(pko + 4ull * i) = p;
+			*reinterpret_cast<gu32_w *>(pko + 4ull * i) = p;
 			if ((head >> k) & 1)
-				*reinterpret_cast<fr_gu32x4_w *>(heads + 16ull * p) = rec[k];
+				*reinterpret_cast<gu32x4_w *>(heads + 16ull * p) = rec[k];
 		}
-		__syncthreads();   // s_tile / s_cnt reuse
+		__syncthreads();   // s_cnt / the ticket's word reused
 	}
 }
 
@@ -180,15 +130,8 @@ __global__ __launch_bounds__(256) void xfg_frags_spread_kernel(
 
 extern "C" int xfg_launch_frags_heads(const struct xfg_frags_kargs *a, unsigned grid, void *stream)
 {
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	const uint64_t ntiles = XFG_FRAGS_TILES(a->n);
-	if (hipMemsetAsync(a->state, 0, XFG_FRAGS_STATE_WORDS(a->n) * 8, s) != hipSuccess)
-		return -5;
-	if (grid > ntiles)
-		grid = (unsigned)ntiles;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_frags_heads_kernel, dim3(grid), dim3(FR_LANES), 0, s, *a);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
+	return xfg_scan_launch(xfg_frags_heads_kernel, a->state, XFG_FRAGS_STATE_WORDS(a->n),
+			       XFG_FRAGS_TILES(a->n), grid, static_cast<hipStream_t>(stream), *a);
 }
 
 extern "C" int xfg_launch_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *verdicts,

@@ -2072,20 +2072,19 @@ extern "C" int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
 	return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
+// the tile scan's pieces: ticket, ballot rank, look-back, launch
+#include "xfg_scan.hip"
+
 // ---------------------------------------------------------------- verdict compaction
 // The indices of the packets whose verdict equals `action`, in packet order
 // (the PASS list a forwarding stage walks: the reference chains only on
 // XDP_PASS, xdp-filter/xdpfilt_prog.h:209-212).  One pass over the verdict
-// bytes: a workgroup takes tiles of CT_TILE verdicts in ticket order; each
-// lane counts its 16 bytes, wave prefix sums (shuffles) and an LDS step give
-// the workgroup's offsets, and a decoupled look-back over the earlier tiles'
-// published {flag, sum} words gives the tile's base.  A status word packs
-// flag (bits 62-63: 1 = tile aggregate, 2 = inclusive prefix) and value, so
-// one 8-byte agent-scope atomic carries both.
+// bytes in the tile scan's scheme (xfg_scan.hip), tiles of CT_TILE verdicts:
+// each lane counts its 16 bytes, wave prefix sums (shuffles) and an LDS step
+// give the workgroup's offsets, the look-back the tile's base.
 namespace {
-constexpr int CT_LANES = 256;
+constexpr int CT_LANES = SC_LANES;
 constexpr int CT_TILE = CT_LANES * 16;
-constexpr unsigned long long CT_AGG = 1ull << 62, CT_INC = 2ull << 62, CT_VAL = (1ull << 62) - 1;
 
 __device__ __forceinline__ uint32_t count_eq(uint32_t w, uint32_t act4)
 {
@@ -2098,20 +2097,17 @@ __device__ __forceinline__ uint32_t count_eq(uint32_t w, uint32_t act4)
 __global__ __launch_bounds__(CT_LANES) void xfg_compact_kernel(
 	const uint8_t *__restrict__ verdicts, uint64_t n, uint32_t action,
 	uint32_t *__restrict__ idx, unsigned long long *__restrict__ count,
-	unsigned long long *status, uint32_t *ticket, uint64_t ntiles)
+	unsigned long long *status, uint32_t *ticket, uint32_t ntiles)
 {
 	__shared__ uint32_t s_wave[CT_LANES / 64];
-	__shared__ uint64_t s_tile, s_base;
+	__shared__ uint64_t s_base;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const uint32_t act4 = action * 0x01010101u;
 	for (;;) {
-		if (tid == 0)
-			s_tile = atomicAdd(ticket, 1u);
-		__syncthreads();
-		const uint64_t t = s_tile;
+		const uint32_t t = xfg_tile_ticket(ticket);
 		if (t >= ntiles)
 			break;
-		const uint64_t first = t * CT_TILE + (uint64_t)tid * 16;
+		const uint64_t first = (uint64_t)t * CT_TILE + (uint64_t)tid * 16;
 		uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
 		uint32_t valid = 0;   // bytes of this lane inside the batch
 		if (first + 16 <= n) {
@@ -2156,32 +2152,8 @@ __global__ __launch_bounds__(CT_LANES) void xfg_compact_kernel(
 			before += k < wave ? s_wave[k] : 0;
 			agg += s_wave[k];
 		}
-		// decoupled look-back (one lane): publish the aggregate, walk back
 		if (tid == 0) {
-			unsigned long long base = 0;
-			if (t == 0) {
-				__hip_atomic_store(&status[0], CT_INC | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			} else {
-				__hip_atomic_store(&status[t], CT_AGG | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-				for (uint64_t p = t - 1;;) {
-					const unsigned long long w = __hip_atomic_load(
-						&status[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					if (w & CT_INC) {
-						base += w & CT_VAL;
-						break;
-					}
-					if (w & CT_AGG) {
-						base += w & CT_VAL;
-						p--;   // tile 0 always publishes CT_INC
-						continue;
-					}
-					__builtin_amdgcn_s_sleep(1);   // predecessor still counting
-				}
-				__hip_atomic_store(&status[t], CT_INC | (base + agg), __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			}
+			const unsigned long long base = xfg_lookback<false>(status, t, agg);
 			s_base = base;
 			if (t == ntiles - 1)
 				*count = base + agg;
@@ -2193,7 +2165,7 @@ __global__ __launch_bounds__(CT_LANES) void xfg_compact_kernel(
 				if (byte_at(k) == action)
 					idx[pos++] = (uint32_t)(first + k);
 		}
-		__syncthreads();   // s_tile / s_wave reuse
+		__syncthreads();   // s_wave / the ticket's word reused
 	}
 }
 
@@ -2204,15 +2176,12 @@ extern "C" int xfg_launch_compact(const uint8_t *verdicts, uint64_t n, uint32_t 
 {
 	hipStream_t s = static_cast<hipStream_t>(stream);
 	const uint64_t ntiles = (n + CT_TILE - 1) / CT_TILE;
-	if (hipMemsetAsync(status, 0, ntiles * 8, s) != hipSuccess ||
-	    hipMemsetAsync(ticket, 0, 4, s) != hipSuccess)
+	if (hipMemsetAsync(ticket, 0, 4, s) != hipSuccess)
 		return -5;
 	if (!n)
 		return hipMemsetAsync(count, 0, 8, s) == hipSuccess ? 0 : -5;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_compact_kernel, dim3(grid), dim3(CT_LANES), 0, s, verdicts, n, action,
-			   idx, count, status, ticket, ntiles);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
+	return xfg_scan_launch(xfg_compact_kernel, status, ntiles, ntiles, grid, s, verdicts, n, action,
+			       idx, count, status, ticket, (uint32_t)ntiles);
 }
 
 extern "C" uint64_t xfg_compact_tiles(uint64_t n)
@@ -2220,8 +2189,8 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 	return (n + CT_TILE - 1) / CT_TILE;
 }
 
-// AF_XDP egress (TX and fill ring records from verdicts): the same tile
-// scheme and status words over 16-byte records
+// AF_XDP egress (TX and fill ring records from verdicts): the tile scan over
+// 16-byte records
 #include "xfg_egress.hip"
 
 // capture by verdict (pcapng blocks of the selected frames): the same scheme

@@ -17,12 +17,9 @@
 // record; the classify kernels then take flat as a plain descriptor array.
 //
 // Egress: xfg_egress.hip's one-pass order-preserving partition, segmented by
-// socket.  A workgroup takes tiles of XFG_SOCKS_TILE flat records in ticket
-// order; in pass k lane l owns flat record tile * T + k * 256 + l.  A record
-// counts as PASS if its verdict is XDP_PASS and its socket has a TX ring.  A
-// ballot gives the PASS records before it in its wave and pass, an LDS step
-// those in the tile, a decoupled look-back over the earlier tiles' {flag, sum}
-// status words the tile's base: np(i), the PASS records before flat index i.
+// socket: the tile scan (xfg_scan.hip) over tiles of XFG_SOCKS_TILE flat
+// records.  A record counts as PASS if its verdict is XDP_PASS and its socket
+// has a TX ring; the scan gives np(i), the PASS records before flat index i.
 // A record's TX rank in its socket is np(i) - np(base[s]); its fill rank is
 // (i - base[s]) minus that in its socket's own fill ring, i - np(i) in the
 // shared one.  What remains is np(base[s]):
@@ -38,33 +35,20 @@
 // ones too (the last tile also for bases equal to n, the total among them), so
 // the last tile can write the counts as differences of consecutive words.
 //
-// Progress: a tile waits only for words of tiles with lower numbers -- the
-// look-back for status words of earlier tiles, the carry for the tile that
-// owns an earlier flat index, the last tile's counts for all the others.
-// Tile numbers are tickets, so a lower one was drawn earlier, by a workgroup
-// that is running; and what that workgroup publishes needs, in turn, only
-// lower tiles.  By induction from tile 0, which waits for nothing, every wait
-// ends.  (The grid is also no larger than what is resident.)  A wait is still
-// bounded (XFG_SOCKS_SPINS polls, far past any real one): it gives up with
-// state word 1 set rather than hold the device.
+// Progress (xfg_scan.hip): beside the look-back a tile waits for the carry,
+// a word of the tile that owns an earlier flat index, and the last tile's
+// counts for words of all the others -- tiles with lower numbers all.  Every
+// wait is still bounded (XFG_SOCKS_SPINS polls, far past any real one): it
+// gives up with state word 1 set rather than hold the device.
 //
-// XFG_EGRESS_SWAP_MACS: as in xfg_egress.hip, for the records that count as
-// PASS.
+// XFG_EGRESS_SWAP_MACS: for the records that count as PASS.
 //
 // Not here: multi-buffer packets (xfg_socks_frags.hip, which reuses this
 // file's table, search and waits), sockets over different UMEMs.
 
 namespace {
-constexpr int SK_LANES = 256;
-constexpr int SK_PASSES = 8;
-constexpr int SK_WAVES = SK_LANES / 64;
-constexpr int SK_SLOTS = SK_PASSES * SK_WAVES;   // (pass, wave) pairs: 64 records each
-static_assert(SK_LANES * SK_PASSES == XFG_SOCKS_TILE, "tile shape");
+static_assert(SC_LANES * SC_PASSES == XFG_SOCKS_TILE, "tile shape");
 constexpr unsigned long long SK_SET = 1ull << 63;   // a published np(base[s]) word
-
-typedef const __attribute__((address_space(1))) u32x4 sk_gring;   // struct xfg_sock_ring
-typedef const __attribute__((address_space(1))) uint32_t sk_gu32;
-typedef __attribute__((address_space(1))) u32x4 sk_gu32x4_w;
 
 // the socket of flat record i < base[nsocks]: the last s with base[s] <= i
 __device__ __forceinline__ uint32_t sk_find(const uint32_t *base, uint32_t nsocks, uint32_t i)
@@ -82,8 +66,8 @@ __device__ __forceinline__ uint32_t sk_find(const uint32_t *base, uint32_t nsock
 
 __device__ __forceinline__ u32x4 sk_ring(const xfg_sock_ent *ents, uint32_t s, int which)
 {
-	return *reinterpret_cast<sk_gring *>((uint64_t)(uintptr_t)ents +
-					     (uint64_t)s * sizeof(xfg_sock_ent) + 16u * which);
+	return *reinterpret_cast<gu32x4 *>((uint64_t)(uintptr_t)ents +
+					   (uint64_t)s * sizeof(xfg_sock_ent) + 16u * which);
 }
 
 // a published word's value, once it is set (if it never is: 0, state word 1
@@ -108,7 +92,7 @@ __global__ __launch_bounds__(256) void xfg_socks_gather_kernel(const xfg_socks_g
 {
 	__shared__ uint32_t s_sbase[XFG_SOCKS_TABLE_MAX + 1];
 	for (uint32_t s = threadIdx.x; s <= a.nsocks; s += 256)
-		s_sbase[s] = *reinterpret_cast<sk_gu32 *>((uint64_t)(uintptr_t)a.base + 4ull * s);
+		s_sbase[s] = *reinterpret_cast<gu32 *>((uint64_t)(uintptr_t)a.base + 4ull * s);
 	__syncthreads();
 	const uint64_t flat = (uint64_t)(uintptr_t)a.flat;
 	const uint64_t step = (uint64_t)gridDim.x * 256;
@@ -118,18 +102,18 @@ __global__ __launch_bounds__(256) void xfg_socks_gather_kernel(const xfg_socks_g
 		const uint64_t p = (uint64_t)rx.y << 32 | rx.x;
 		const u32x4 rec = __builtin_nontemporal_load(reinterpret_cast<gdesc *>(
 			p + 16ull * ((rx.z + ((uint32_t)i - s_sbase[s])) & rx.w)));
-		*reinterpret_cast<sk_gu32x4_w *>(flat + 16ull * i) = rec;
+		*reinterpret_cast<gu32x4_w *>(flat + 16ull * i) = rec;
 	}
 }
 
-__global__ __launch_bounds__(SK_LANES) void xfg_socks_egress_kernel(const xfg_socks_kargs a)
+__global__ __launch_bounds__(SC_LANES) void xfg_socks_egress_kernel(const xfg_socks_kargs a)
 {
 	__shared__ uint32_t s_sbase[XFG_SOCKS_TABLE_MAX + 1];
-	__shared__ unsigned long long s_bal[SK_SLOTS + 1];   // ([SK_SLOTS]: 0, the tile's end)
-	__shared__ uint32_t s_cnt[SK_SLOTS];
-	__shared__ uint32_t s_pre[SK_SLOTS + 1];             // s_cnt's exclusive prefix sums
-	__shared__ uint32_t s_tile, s_base, s_carry, s_ok;
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	__shared__ unsigned long long s_bal[SC_SLOTS + 1];   // ([SC_SLOTS]: 0, the tile's end)
+	__shared__ uint32_t s_cnt[SC_SLOTS];
+	__shared__ uint32_t s_pre[SC_SLOTS + 1];             // s_cnt's exclusive prefix sums
+	__shared__ uint32_t s_base, s_carry, s_ok;
+	const int tid = threadIdx.x;
 	const uint32_t n = a.n, nsocks = a.nsocks;
 	const uint32_t ntiles = (uint32_t)XFG_SOCKS_TILES(n);
 	uint32_t *ticket = reinterpret_cast<uint32_t *>(a.state);
@@ -137,31 +121,24 @@ __global__ __launch_bounds__(SK_LANES) void xfg_socks_egress_kernel(const xfg_so
 	unsigned long long *pub = status + ntiles;   // nsocks + 1 words
 	const uint64_t fill = (uint64_t)(uintptr_t)a.fill, umem = (uint64_t)(uintptr_t)a.umem;
 	const uint64_t vd = (uint64_t)(uintptr_t)a.verdicts;
-	for (uint32_t s = tid; s <= nsocks; s += SK_LANES)
-		s_sbase[s] = *reinterpret_cast<sk_gu32 *>((uint64_t)(uintptr_t)a.base + 4ull * s);
+	for (uint32_t s = tid; s <= nsocks; s += SC_LANES)
+		s_sbase[s] = *reinterpret_cast<gu32 *>((uint64_t)(uintptr_t)a.base + 4ull * s);
 	if (tid == 0)
-		s_bal[SK_SLOTS] = 0;
-	// PASS records of the tile before its position p (0 .. T; after the barrier
-	// that follows the prefix sums)
-	auto tile_before = [&](uint32_t p) -> uint32_t {
-		return s_pre[p >> 6] + __builtin_popcountll(s_bal[p >> 6] & ((1ull << (p & 63)) - 1));
-	};
+		s_bal[SC_SLOTS] = 0;
 	for (;;) {
-		if (tid == 0)
-			s_tile = atomicAdd(ticket, 1u);
-		__syncthreads();   // (the first one also: the bases are staged)
-		const uint32_t t = s_tile;
+		// (the first ticket's barrier also: the bases are staged)
+		const uint32_t t = xfg_tile_ticket(ticket);
 		if (t >= ntiles)
 			break;
 		const uint32_t t0 = t * XFG_SOCKS_TILE;   // (< n)
 		// (64-bit: the last tile's lanes past the batch may pass 2^32)
 		const uint64_t i0 = (uint64_t)t0 + tid;
-		uint32_t sock[SK_PASSES];
-		u32x4 rec[SK_PASSES];
+		uint32_t sock[SC_PASSES];
+		u32x4 rec[SC_PASSES];
 		uint32_t pass = 0;   // bit k: the record of pass k goes to its socket's TX ring
 #pragma unroll
-		for (int k = 0; k < SK_PASSES; k++) {
-			const uint64_t i = i0 + (uint64_t)k * SK_LANES;
+		for (int k = 0; k < SC_PASSES; k++) {
+			const uint64_t i = i0 + (uint64_t)k * SC_LANES;
 			sock[k] = 0;
 			rec[k] = u32x4{ 0, 0, 0, 0 };
 			if (i < n) {
@@ -177,89 +154,32 @@ __global__ __launch_bounds__(SK_LANES) void xfg_socks_egress_kernel(const xfg_so
 			}
 		}
 		// PASS records before this lane's record of pass k: in its wave ...
-		uint32_t before[SK_PASSES];
+		uint32_t before[SC_PASSES];
 #pragma unroll
-		for (int k = 0; k < SK_PASSES; k++) {
-			const uint64_t b = __ballot((pass >> k) & 1);
-			before[k] = __builtin_amdgcn_mbcnt_hi(
-				(uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-			if (lane == 0) {
-				s_bal[k * SK_WAVES + wave] = b;
-				s_cnt[k * SK_WAVES + wave] = __builtin_popcountll(b);
-			}
-		}
+		for (int k = 0; k < SC_PASSES; k++)
+			xfg_wave_rank<true>((pass >> k) & 1, k, before[k], s_cnt, s_bal);
 		__syncthreads();
-		// ... and in the tile (flat order: pass, wave, lane)
-		uint32_t agg = 0;
-#pragma unroll
-		for (int k = 0; k < SK_PASSES; k++) {
-#pragma unroll
-			for (int w = 0; w < SK_WAVES; w++) {
-				if (w == wave)
-					before[k] += agg;
-				if (tid == k * SK_WAVES + w)
-					s_pre[tid] = agg;   // (for positions that are not the lane's own)
-				agg += s_cnt[k * SK_WAVES + w];
-			}
-		}
-		if (tid == SK_SLOTS)
-			s_pre[SK_SLOTS] = agg;
+		// ... and in the tile, with the slots' sums for positions that are not
+		// the lane's own
+		const uint32_t agg = xfg_tile_step<true>(before, s_cnt, s_pre);
 		if (a.swap_macs) {
 #pragma unroll
-			for (int k = 0; k < SK_PASSES; k++) {
-				if (!((pass >> k) & 1))
-					continue;
-				const uint64_t addr = (uint64_t)rec[k].y << 32 | rec[k].x;
-				gu32x4_w *p = reinterpret_cast<gu32x4_w *>(umem + (addr & EG_ADDR) +
-									   (addr >> 48));
-				const u32x4 h = *p;
-				*p = u32x4{ (h.y >> 16) | (h.z << 16), (h.z >> 16) | (h.x << 16),
-					    (h.x >> 16) | (h.y << 16), h.w };
+			for (int k = 0; k < SC_PASSES; k++) {
+				if ((pass >> k) & 1)
+					xfg_swap_macs(umem, (uint64_t)rec[k].y << 32 | rec[k].x);
 			}
 		}
-		// decoupled look-back (one lane): publish the aggregate, walk back
-		if (tid == 0) {
-			unsigned long long base = 0;
-			if (t == 0) {
-				__hip_atomic_store(&status[0], CT_INC | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			} else {
-				__hip_atomic_store(&status[t], CT_AGG | agg, __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-				uint32_t spins = 0;
-				for (uint32_t p = t - 1;;) {
-					const unsigned long long w = __hip_atomic_load(
-						&status[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					if (w & CT_INC) {
-						base += w & CT_VAL;
-						break;
-					}
-					if (w & CT_AGG) {
-						base += w & CT_VAL;
-						p--;   // tile 0 always publishes CT_INC
-						continue;
-					}
-					if (++spins == XFG_SOCKS_SPINS) {
-						__hip_atomic_store(&a.state[1], 1ull, __ATOMIC_RELAXED,
-								   __HIP_MEMORY_SCOPE_AGENT);
-						break;
-					}
-					__builtin_amdgcn_s_sleep(1);   // predecessor still counting
-				}
-				__hip_atomic_store(&status[t], CT_INC | (base + agg), __ATOMIC_RELAXED,
-						   __HIP_MEMORY_SCOPE_AGENT);
-			}
-			s_base = (uint32_t)base;   // (<= n < 2^32)
-		}
+		if (tid == 0)   // (<= n < 2^32)
+			s_base = (uint32_t)xfg_lookback<true>(status, t, agg, &a.state[1]);
 		__syncthreads();
 		const uint32_t base = s_base;
 		// np(base[s]) of the sockets whose base lies in this tile, for the tiles
 		// they are carried into and for the counts (the last tile: the bases
 		// equal to n too, at position T when the batch fills the tile)
-		for (uint32_t s = tid; s <= nsocks; s += SK_LANES) {
+		for (uint32_t s = tid; s <= nsocks; s += SC_LANES) {
 			const uint32_t b = s_sbase[s];
 			if (b >= t0 && (b - t0 < XFG_SOCKS_TILE || t == ntiles - 1))
-				__hip_atomic_store(&pub[s], SK_SET | (base + tile_before(b - t0)),
+				__hip_atomic_store(&pub[s], SK_SET | (base + xfg_tile_before(s_pre, s_bal, b - t0)),
 						   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		}
 		// the socket carried into the tile, if its first record's starts before it
@@ -276,14 +196,14 @@ __global__ __launch_bounds__(SK_LANES) void xfg_socks_egress_kernel(const xfg_so
 		const uint32_t carry = s_carry;
 		const bool ok = s_ok;
 #pragma unroll
-		for (int k = 0; k < SK_PASSES; k++) {
-			const uint64_t i = i0 + (uint64_t)k * SK_LANES;
+		for (int k = 0; k < SC_PASSES; k++) {
+			const uint64_t i = i0 + (uint64_t)k * SC_LANES;
 			if (i >= n || !ok)
 				continue;
 			const uint32_t s = sock[k], b = s_sbase[s];
 			const uint32_t np = base + before[k];   // PASS records before flat record i
 			// ... and of them, those in its own socket
-			const uint32_t r = np - (b < t0 ? carry : base + tile_before(b - t0));
+			const uint32_t r = np - (b < t0 ? carry : base + xfg_tile_before(s_pre, s_bal, b - t0));
 			const uint64_t addr = (uint64_t)rec[k].y << 32 | rec[k].x;
 			if ((pass >> k) & 1) {
 				const u32x4 tx = sk_ring(a.ents, s, 1);
@@ -293,19 +213,19 @@ __global__ __launch_bounds__(SK_LANES) void xfg_socks_egress_kernel(const xfg_so
 			} else if (fill) {
 				*reinterpret_cast<gu64_w *>(
 					fill + 8ull * ((a.fill_first + ((uint32_t)i - np)) & a.fill_mask)) =
-					addr & EG_ADDR;
+					addr & XSK_ADDR;
 			} else {
 				const u32x4 fr = sk_ring(a.ents, s, 2);
 				if (fr.x | fr.y)
 					*reinterpret_cast<gu64_w *>(
 						((uint64_t)fr.y << 32 | fr.x) +
-						8ull * ((fr.z + (((uint32_t)i - b) - r)) & fr.w)) = addr & EG_ADDR;
+						8ull * ((fr.z + (((uint32_t)i - b) - r)) & fr.w)) = addr & XSK_ADDR;
 			}
 		}
 		// the counts: every socket's word is published by now or will be, by a
 		// tile with a lower number (this tile's own: before the barrier above)
 		if (t == ntiles - 1) {
-			for (uint32_t s = tid; s <= nsocks; s += SK_LANES) {
+			for (uint32_t s = tid; s <= nsocks; s += SC_LANES) {
 				uint32_t got = 1;
 				const uint32_t lo = sk_wait(&pub[s], a.state, &got);
 				if (s == nsocks) {
@@ -318,7 +238,7 @@ __global__ __launch_bounds__(SK_LANES) void xfg_socks_egress_kernel(const xfg_so
 				}
 			}
 		}
-		__syncthreads();   // s_tile / s_cnt / s_bal reuse
+		__syncthreads();   // s_cnt / s_bal / the ticket's word reused
 	}
 }
 
@@ -336,13 +256,6 @@ extern "C" int xfg_launch_socks_gather(const struct xfg_socks_gather_kargs *a, u
 
 extern "C" int xfg_launch_socks_egress(const struct xfg_socks_kargs *a, unsigned grid, void *stream)
 {
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	const uint64_t ntiles = XFG_SOCKS_TILES(a->n);
-	if (hipMemsetAsync(a->state, 0, XFG_SOCKS_STATE_WORDS(a->n, a->nsocks) * 8, s) != hipSuccess)
-		return -5;
-	if (grid > ntiles)
-		grid = (unsigned)ntiles;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_socks_egress_kernel, dim3(grid), dim3(SK_LANES), 0, s, *a);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
+	return xfg_scan_launch(xfg_socks_egress_kernel, a->state, XFG_SOCKS_STATE_WORDS(a->n, a->nsocks),
+			       XFG_SOCKS_TILES(a->n), grid, static_cast<hipStream_t>(stream), *a);
 }
