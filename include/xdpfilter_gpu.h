@@ -300,6 +300,83 @@ int xfg_classify_descs_frags(xfg_ctx *ctx, int dev, const struct xfg_desc_batch 
 			     struct xfg_frags *fr, uint8_t *verdicts, void *stream);
 
 /*
+ * Chained contexts: run this context's program only on the frames an earlier
+ * stage passed on.  xdp-filter is never the last word on a packet: it chains
+ * on XDP_PASS (xdp-filter/xdpfilt_prog.h:209-212), and the dispatcher runs the
+ * next program only on a frame whose return value is in the previous
+ * program's chain_call_actions (lib/libxdp/xdp-dispatcher.c.in:59-79: if
+ * (!((1U << ret) & conf.chain_call_actions[i])) return ret;).  Two stages
+ * express what one program cannot, e.g. an allow-list context for ports
+ * followed by a deny-list context for addresses.
+ *
+ * @verdicts (device, count bytes) is input and output: what an earlier stage
+ * wrote for the same batch -- another context, or this one.  Frame i is
+ * selected if its byte v = verdicts[i] is below 32 and bit v of chain_mask is
+ * set (xfg_capture's rule for its action_mask); XFG_VERDICT_NONE and every
+ * other byte >= 32 is never selected.  The verdicts, rule hit counts and
+ * per-action statistics of THIS context are exactly those of running its
+ * program on the selected frames alone, in their order.  A selected frame's
+ * byte is replaced by the new verdict; every other byte of @verdicts is left
+ * as it was.  The earlier stage's context is not touched: as in the
+ * dispatcher, each program keeps its own statistics.
+ *
+ * Out: counts[0] = frames selected, counts[1] = frames not selected
+ * (counts[0] + counts[1] == count); HOST memory, valid when the call returns.
+ * idx (device, count x u32, or NULL): the selected frames' indices, ascending,
+ * counts[0] of them.
+ *
+ * Three steps on the device, as for xfg_classify_descs_frags: a select pass
+ * over the verdict bytes (one kernel: idx and the selected frames as a plain
+ * descriptor array in library scratch -- a descriptor batch's records as
+ * received; a struct xfg_batch's frames as {addr = the byte offset from data,
+ * i * stride or offsets[i]; len = min(lens[i], stride) for a fixed stride,
+ * else lens[i]; options = 0}); the selected count read back to the host; the
+ * counts[0] descriptors classified as xfg_classify_descs classifies a plain
+ * array of that many records over umem (or data) -- xfg_last_path and
+ * xfg_open_opts.descs_min_packets behave as for such a call -- and their
+ * verdicts scattered to verdicts[idx[k]].  So a fixed-stride batch chained
+ * this way runs the descriptor kernels (the generic pipelined kernel, or the
+ * general one), not the quotient-index loop of xfg_classify.  The read-back is
+ * the call's one host synchronisation, after it has ordered itself behind
+ * @stream, and deliberate for the reason given at xfg_classify_descs_frags:
+ * the classify launch is planned on the host from the frame count.  The
+ * classify and the scatter are stream-ordered; the call returns without
+ * waiting for them, and @stream's later work runs after them.
+ *
+ * -EINVAL: what the matching unchained call refuses, ch == NULL, sz below the
+ * structure's size, a non-zero flags, idx not 4-byte aligned, verdicts == NULL
+ * with count != 0, count >= 2^32, a fixed-stride batch of more than 2^48 bytes.
+ * count == 0: counts {0, 0}, nothing launched, whatever the context's devices.
+ * -ENODEV on a host-only context, after these checks; no device pointer is
+ * touched before it.  chain_mask == 0 or no frame selected: counts {0, count},
+ * nothing classified, no statistic changes, verdicts untouched.
+ *
+ * Unchecked precondition: with offsets, every offset is below 2^48 -- it
+ * travels in a descriptor's address field, and the device cannot refuse it.
+ *
+ * Many sockets need nothing of their own: with xfg_socks.flat given,
+ * xfg_classify_socks leaves a plain descriptor array, and
+ * xfg_classify_descs_chain takes it.  Not covered: multi-buffer batches (a
+ * chained stage would have to select head records only and spread again), the
+ * host-memory path, and the CLI.
+ */
+#define XFG_CHAIN_PASS (1u << XFG_XDP_PASS)   /* xdp-filter's own chain_call_actions */
+
+struct xfg_chain {
+	size_t sz;            /* sizeof(struct xfg_chain), for extension */
+	uint32_t chain_mask;  /* bit v: a frame whose verdict byte is v (< 32) runs this context's program */
+	uint32_t flags;       /* 0; any bit set: -EINVAL */
+	uint32_t *idx;        /* device, count x u32, 4-byte aligned, or NULL (library scratch):
+	                       * out, the selected frames' indices, ascending */
+	uint64_t counts[2];   /* HOST, out: frames selected, frames not selected */
+};
+
+int xfg_classify_chain(xfg_ctx *ctx, int dev, const struct xfg_batch *batch,
+		       struct xfg_chain *ch, uint8_t *verdicts, void *stream);
+int xfg_classify_descs_chain(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
+			     struct xfg_chain *ch, uint8_t *verdicts, void *stream);
+
+/*
  * Host-resident batch (struct xfg_batch in host memory): classifies it on
  * device @dev and writes the verdicts to host memory.  Only each frame's
  * first 128 bytes (its header window) and its length cross PCIe -- gathered
@@ -816,6 +893,11 @@ int xfg_classify_descs_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch 
  * run). */
 int xfg_classify_descs_frags_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
 				   struct xfg_frags *fr, uint8_t *verdicts, double ms[3]);
+/* One xfg_classify_descs_chain call on the library's stream, timed the same
+ * way: ms[0] the select pass, ms[1] the classify of the selected frames, ms[2]
+ * the scatter (0 for a step that did not run). */
+int xfg_classify_descs_chain_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
+				   struct xfg_chain *ch, uint8_t *verdicts, double ms[3]);
 
 /* Streaming-read probe: average duration of a kernel that reads @bytes of
  * device memory at @src with 16-byte non-temporal loads (the achievable HBM

@@ -31,6 +31,14 @@
       (xfg_capture_descs, snaplen 0), beside xfg_compact; the same ring with
       1514-byte frames at snaplen 96, one in ten selected; one tile of
       packets for the fixed cost of a call -- timed as c3f's legs are
+  c3ch c3d's batch as the second stage of a chain (xfg_classify_descs_chain):
+      the verdict bytes pre-set so that half the frames are selected, once
+      every other frame and once a contiguous half.  The call by wall clock (to
+      its return and to the stream's end) and its three steps
+      (xfg_classify_descs_chain_timed); beside them xfg_classify_descs over a
+      pre-built plain array of the same selected half (stage 2 alone: the
+      floor), over the whole batch, and xfg_compact over the same verdict
+      bytes, with the bytes the select pass and the compaction move
   c3m  c3d's UMEM and rules with every C3 frame the head of a 3-record packet
       (XDP_PKT_CONTD, a socket bound with XDP_USE_SG): two continuation chunks a
       packet, each holding a frame that hits a rule -- 2^22 packets, 3 * 2^22
@@ -306,6 +314,89 @@ def run_c3f(args):
         gbs = moved[k] / (best * 1e-3) / 1e9
         line[k] = {"ms": [round(m, 4) for m in ms[k]], "bytes": moved[k], "GBps": round(gbs, 1),
                    "frac_of_stream_read": round(gbs / read_gbs, 3)}
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
+def run_c3ch(args):
+    """c3d's batch as a chained second stage, half the frames selected."""
+    import numpy as np
+    import torch
+    w = c3d_workload(args, "c3ch")
+    f, n, entries, first = w.f, w.n, w.entries, w.first
+    ring = dict(first=first, mask=entries - 1)
+    runs = max(1, args.runs)
+    d_idx, d_c, d_half = f.alloc(4 * n), f.alloc(16), f.alloc(16 * (n // 2))
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    recs = np.zeros((n, 2), np.uint64)
+    recs[:, 0] = w.perm.astype(np.uint64) * np.uint64(C3D_CHUNK) + np.uint64(C3D_HEADROOM)
+    recs[:, 1] = w.lens.astype(np.uint64)
+
+    def on_stream(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            call()
+        e0.record(stream)
+        for _ in range(args.iters):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    f.classify_descs_timed(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, 2, **ring)
+    whole = [f.classify_descs_timed(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, args.iters, **ring)
+             for _ in range(runs)]
+    line = {"config": "c3ch", "program": f.prog_name, "packets": n, "selected": n // 2,
+            "ring_entries": entries, "iters": args.iters, "runs": runs,
+            "classify_descs_whole_ms": [round(m, 4) for m in whole], "setup_s": round(w.setup_s, 1)}
+    for name in ("alternating", "contiguous"):
+        pre = np.ones(n, np.uint8)                 # DROP: not selected by XFG_CHAIN_PASS
+        if name == "alternating":
+            pre[0::2] = 2
+        else:
+            pre[n // 4:n // 4 + n // 2] = 2
+        sel = np.flatnonzero(pre == 2)
+        assert len(sel) == n // 2
+        d_half.upload(recs[sel])
+        f.classify_descs_timed(w.d_umem.ptr, d_half.ptr, n // 2, d_idx.ptr, 2)
+        floor = [f.classify_descs_timed(w.d_umem.ptr, d_half.ptr, n // 2, d_idx.ptr, args.iters)
+                 for _ in range(runs)]
+        floor_path = f.last_path()
+        w.d_verd.upload(pre)
+        compact = [on_stream(lambda: f.compact(w.d_verd.ptr, n, 2, d_idx.ptr, d_c.ptr, stream=sp))
+                   for _ in range(runs)]
+        steps, ret_ms, end_ms = [], [], []
+        for k in range(runs + 1):                  # (the first call grows the scratch: not counted)
+            w.d_verd.upload(pre)
+            f.sync()
+            counts, ms = f.classify_descs_chain_timed(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, **ring)
+            assert counts == (n // 2, n - n // 2), counts
+            w.d_verd.upload(pre)
+            f.sync()
+            t0 = time.perf_counter()
+            f.classify_descs_chain(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, **ring)
+            t1 = time.perf_counter()
+            f.sync()
+            t2 = time.perf_counter()
+            if k:
+                steps.append([round(m, 4) for m in ms])
+                ret_ms.append(round((t1 - t0) * 1e3, 4))
+                end_ms.append(round((t2 - t0) * 1e3, 4))
+        nsel = n // 2
+        best = [min(s[j] for s in steps) for j in range(3)]
+        sel_bytes, cmp_bytes = n + 16 * nsel + 16 * nsel + 4 * nsel, n + 4 * nsel
+        line[name] = {
+            "chain_steps_ms": steps, "chain_path": f.last_path(),
+            "chain_wall_to_return_ms": ret_ms, "chain_wall_to_stream_end_ms": end_ms,
+            "classify_descs_selected_half_ms": [round(m, 4) for m in floor], "floor_path": floor_path,
+            "compact_ms": [round(m, 4) for m in compact],
+            "overhead_over_floor_ms": round(min(end_ms) - min(floor), 4),
+            "select_plus_scatter_ms": round(best[0] + best[2], 4),
+            "select_bytes": sel_bytes, "compact_bytes": cmp_bytes,
+            "select_GBps": round(sel_bytes / (best[0] * 1e-3) / 1e9, 1),
+            "compact_GBps": round(cmp_bytes / (min(compact) * 1e-3) / 1e9, 1),
+            "select_over_compact": round(best[0] / min(compact), 3)}
     f.close()
     print(json.dumps(line), flush=True)
 
@@ -921,6 +1012,8 @@ def run(name, args):
         return run_c1(args)
     if name == "c3c":
         return run_c3c(args)
+    if name == "c3ch":
+        return run_c3ch(args)
     if name == "c3d":
         return run_c3d(args)
     if name == "c3f":

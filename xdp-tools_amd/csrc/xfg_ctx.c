@@ -47,6 +47,9 @@ int xfg_launch_capture_frags(const struct xfg_capture_frags_kargs *a, unsigned g
 int xfg_launch_frags_heads(const struct xfg_frags_kargs *a, unsigned grid, void *stream);
 int xfg_launch_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *verdicts,
 			    uint32_t done, unsigned grid, void *stream);
+int xfg_launch_chain_select(const struct xfg_chain_kargs *a, unsigned grid, void *stream);
+int xfg_launch_chain_scatter(const uint8_t *pv, const uint32_t *idx, uint8_t *verdicts,
+			     uint32_t cnt, unsigned grid, void *stream);
 int xfg_launch_socks_gather(const struct xfg_socks_gather_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_egress(const struct xfg_socks_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_frags_heads(const struct xfg_socks_frags_kargs *a, unsigned grid, void *stream);
@@ -162,7 +165,10 @@ struct xfg_dev {
 	uint32_t *cticket;
 	/* multi-buffer descriptor batches (xfg_classify_descs_frags), one call
 	 * at a time under frags_lock: the head records, the per-packet verdicts
-	 * and, where the caller wants none, the records' packet indices */
+	 * and, where the caller wants none, the records' packet indices.  A
+	 * chained stage (xfg_classify_chain, xfg_classify_descs_chain) has the
+	 * same three under the same lock: its selected frames' descriptors,
+	 * their verdicts and their indices */
 	pthread_mutex_t frags_lock;
 	void *fr_heads;
 	uint8_t *fr_pv;
@@ -1901,6 +1907,22 @@ static int dev_check(const xfg_ctx *ctx, int dev)
 	return 0;
 }
 
+/* what the entry points refuse of a batch's own fields ... */
+static int batch_bad(const struct xfg_batch *b)
+{
+	if (b->count && (!b->data || !b->lens))
+		return 1;
+	if (!b->offsets && b->count && (b->stride == 0 || (b->stride & 15)))
+		return 1;
+	return ((uintptr_t)b->data & 15) != 0;
+}
+
+/* ... and of a descriptor batch's that is not empty */
+static int descs_bad(const struct xfg_desc_batch *db)
+{
+	return !db->umem || !db->descs || ((uintptr_t)db->descs & 7) || (db->mask & (db->mask + 1u));
+}
+
 static int check_batch(xfg_ctx *ctx, int dev, const struct xfg_batch *b, const void *verdicts)
 {
 	if (!ctx || !b || (!verdicts && b->count))
@@ -1908,13 +1930,7 @@ static int check_batch(xfg_ctx *ctx, int dev, const struct xfg_batch *b, const v
 	const int err = dev_check(ctx, dev);
 	if (err)
 		return err;
-	if (b->count && (!b->data || !b->lens))
-		return -EINVAL;
-	if (!b->offsets && b->count && (b->stride == 0 || (b->stride & 15)))
-		return -EINVAL;
-	if (((uintptr_t)b->data & 15))
-		return -EINVAL;
-	return 0;
+	return batch_bad(b) ? -EINVAL : 0;
 }
 
 /* argument checks of the descriptor entry points; 1: an empty batch */
@@ -1927,9 +1943,7 @@ static int check_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db, c
 		return err;
 	if (!db->count)
 		return 1;
-	if (!db->umem || !db->descs || ((uintptr_t)db->descs & 7) || (db->mask & (db->mask + 1u)))
-		return -EINVAL;
-	return 0;
+	return descs_bad(db) ? -EINVAL : 0;
 }
 
 /* The four entry points' body, their arguments checked: @iters launches of
@@ -2257,6 +2271,143 @@ int xfg_classify_descs_frags_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_
 	if (!ms)
 		return -EINVAL;
 	return frags_run(ctx, dev, db, fr, verdicts, NULL, ms);
+}
+
+/* A chained stage (include/xdpfilter_gpu.h) over @b or over @db: frags_run()'s
+ * sequence with the select pass in the head pass's place -- the pass over the
+ * earlier stage's verdict bytes, the selected count read back (the call's one
+ * host synchronisation: the classify launch is planned from it), the selected
+ * frames classified as a plain descriptor array over the batch's bytes through
+ * classify(), and their verdicts scattered to the frames' own bytes.  On the
+ * device's own stream between @stream's earlier and later work, under
+ * frags_lock, whose scratch it uses (the heads' room for the descriptors, the
+ * packet indices' for idx).  The argument checks come first and the empty
+ * batch next, neither needing a device. */
+static int chain_run(xfg_ctx *ctx, int dev, const struct xfg_batch *b,
+		     const struct xfg_desc_batch *db, struct xfg_chain *ch, uint8_t *verdicts,
+		     void *stream, double *ms)
+{
+	if (!ctx || (!b && !db) || !ch || ch->sz < sizeof(*ch) || ch->flags ||
+	    ((uintptr_t)ch->idx & 3))
+		return -EINVAL;
+	const uint64_t n = db ? db->count : b->count;
+	if (n > 0xffffffffull || (n && !verdicts) || (b ? batch_bad(b) : n && descs_bad(db)))
+		return -EINVAL;
+	/* (a frame's offset travels in a descriptor's 48-bit address field) */
+	if (b && !b->offsets && n * b->stride > 1ull << 48)
+		return -EINVAL;
+	if (ms)
+		ms[0] = ms[1] = ms[2] = 0;
+	if (!n) {
+		ch->counts[0] = ch->counts[1] = 0;
+		return 0;
+	}
+	int err = dev_check(ctx, dev);
+	if (err)
+		return err;
+	ch->counts[0] = 0;
+	ch->counts[1] = n;
+	if (!ch->chain_mask)
+		return 0;
+	struct xfg_dev *d = &ctx->dev[dev];
+	unsigned long long got = 0;
+	float t = 0;
+	int entered = 0;
+	pthread_mutex_lock(&d->frags_lock);
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if ((err = cstatus_room(d, XFG_CHAIN_STATE_WORDS(n))) ||
+	    (err = scratch(d, &d->fr_heads, &d->fr_heads_bytes, n * 16)) ||
+	    (err = scratch(d, (void **)&d->fr_pv, &d->fr_pv_bytes, n)) ||
+	    (!ch->idx && (err = scratch(d, (void **)&d->fr_pkt, &d->fr_pkt_bytes, n * 4))))
+		goto fail;
+	uint32_t *idx = ch->idx ? ch->idx : d->fr_pkt;
+	struct xfg_chain_kargs a = {
+		.verdicts = verdicts, .idx = idx, .sel = d->fr_heads, .state = d->cstatus,
+		.n = (uint32_t)n, .chain_mask = ch->chain_mask,
+	};
+	if (db) {
+		a.descs = db->descs;
+		a.first = db->first;
+		a.mask = db->mask;
+		a.form = XFG_CHAIN_F_DESCS;
+	} else {
+		a.offsets = b->offsets;
+		a.lens = b->lens;
+		a.stride = b->stride;
+		a.form = b->lens_u16 ? XFG_CHAIN_F_LENS_U16 : 0;
+	}
+	if ((err = stream_enter(d, stream)))
+		goto fail;
+	entered = 1;
+	if (ms)
+		HIPCHK(hipEventRecord(d->ev0, d->stream));
+	/* (four workgroups a CU: all of them resident) */
+	if ((err = xfg_launch_chain_select(&a, (unsigned)d->ncu * 4, d->stream)))
+		goto fail;
+	if (ms)
+		HIPCHK(hipEventRecord(d->ev1, d->stream));
+	HIPCHK(hipMemcpyAsync(&got, d->cstatus + 2, sizeof(got), hipMemcpyDeviceToHost, d->stream));
+	HIPCHK(hipStreamSynchronize(d->stream));
+	if (ms) {
+		HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
+		ms[0] = t;
+	}
+	if (got > n) {
+		err = -EIO;
+		goto fail;
+	}
+	ch->counts[0] = got;
+	ch->counts[1] = n - got;
+	if (got) {
+		const struct xfg_desc_batch sb = { db ? db->umem : b->data, d->fr_heads, 0, 0xffffffffu,
+						   got };
+		/* (classify() takes d->lock itself) */
+		pthread_mutex_unlock(&d->lock);
+		err = classify(ctx, dev, NULL, &sb, d->fr_pv, NULL, 1, ms ? &ms[1] : NULL);
+		pthread_mutex_lock(&d->lock);
+		if (err)
+			goto fail;
+		HIPCHK(hipSetDevice(d->ordinal));
+		if (ms)
+			HIPCHK(hipEventRecord(d->ev0, d->stream));
+		if ((err = xfg_launch_chain_scatter(d->fr_pv, idx, verdicts, (uint32_t)got,
+						    (unsigned)d->ncu * 8, d->stream)))
+			goto fail;
+		if (ms) {
+			HIPCHK(hipEventRecord(d->ev1, d->stream));
+			HIPCHK(hipEventSynchronize(d->ev1));
+			HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
+			ms[2] = t;
+		}
+	}
+fail:
+	/* (also after an error: the caller's stream behind what was queued) */
+	if (entered) {
+		const int e2 = stream_leave(d, stream);
+		err = err ? err : e2;
+	}
+	pthread_mutex_unlock(&d->lock);
+	pthread_mutex_unlock(&d->frags_lock);
+	return err;
+}
+
+int xfg_classify_chain(xfg_ctx *ctx, int dev, const struct xfg_batch *b, struct xfg_chain *ch,
+		       uint8_t *verdicts, void *stream)
+{
+	return b ? chain_run(ctx, dev, b, NULL, ch, verdicts, stream, NULL) : -EINVAL;
+}
+
+int xfg_classify_descs_chain(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+			     struct xfg_chain *ch, uint8_t *verdicts, void *stream)
+{
+	return db ? chain_run(ctx, dev, NULL, db, ch, verdicts, stream, NULL) : -EINVAL;
+}
+
+int xfg_classify_descs_chain_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+				   struct xfg_chain *ch, uint8_t *verdicts, double ms[3])
+{
+	return db && ms ? chain_run(ctx, dev, NULL, db, ch, verdicts, NULL, ms) : -EINVAL;
 }
 
 /* Many sockets over one UMEM (include/xdpfilter_gpu.h): what both calls check

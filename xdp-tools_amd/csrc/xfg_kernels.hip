@@ -2205,6 +2205,10 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // kernel's scheme over the end-of-packet flags
 #include "xfg_frags.hip"
 
+// chained contexts (select pass by verdict, verdict scatter): the head pass's
+// scheme with the chain mask as the predicate
+#include "xfg_chain.hip"
+
 // many sockets over one UMEM (gather, segmented egress): the egress kernel's
 // scheme with a socket table in the place of one ring
 #include "xfg_socks.hip"

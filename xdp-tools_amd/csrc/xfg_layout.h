@@ -394,6 +394,33 @@ struct xfg_frags_kargs {
 #define XFG_FRAGS_TILES(n) (((uint64_t)(n) + XFG_FRAGS_TILE - 1) / XFG_FRAGS_TILE)
 #define XFG_FRAGS_STATE_WORDS(n) ((XFG_FRAGS_TILES(n) + 5) & ~1ull)
 
+/* Arguments of the select pass of a chained stage (xfg_chain.hip,
+ * xfg_classify_chain() and xfg_classify_descs_chain()): the frames in either
+ * batch form, the earlier stage's verdict bytes, the selection; out, the k-th
+ * selected frame's index idx[k] and its plain struct xdp_desc sel[k] (room for
+ * n each); and the launch's state words laid out as the head pass's -- word 0
+ * the tile ticket, word 2 the selected frames, from word 4 one status word a
+ * tile; zeroed by the launch function. */
+struct xfg_chain_kargs {
+	const uint64_t *offsets;        /* batch form: NULL = fixed stride */
+	const void *lens;               /* batch form */
+	const void *descs;              /* descriptor form: struct xdp_desc records */
+	const uint8_t *verdicts;
+	uint32_t *idx;
+	void *sel;
+	unsigned long long *state;
+	uint32_t n;                     /* frames, >= 1 */
+	uint32_t stride;
+	uint32_t first, mask;           /* descriptor form */
+	uint32_t chain_mask;            /* != 0 */
+	uint32_t form;                  /* XFG_CHAIN_F_* */
+};
+#define XFG_CHAIN_F_DESCS 1u
+#define XFG_CHAIN_F_LENS_U16 2u
+#define XFG_CHAIN_TILE 2048u   /* frames a tile: 256 lanes x 8 passes */
+#define XFG_CHAIN_TILES(n) (((uint64_t)(n) + XFG_CHAIN_TILE - 1) / XFG_CHAIN_TILE)
+#define XFG_CHAIN_STATE_WORDS(n) ((XFG_CHAIN_TILES(n) + 5) & ~1ull)
+
 /* Many sockets over one UMEM (xfg_socks.hip, xfg_classify_socks() and
  * xfg_socks_egress()).  A socket's three rings as the kernels read them, one
  * 16-byte load each; a launch's table in device memory is nsocks of these and,

@@ -65,6 +65,7 @@ EXPORTS = [
     "xfg_ring_egress", "xfg_capture", "xfg_capture_descs", "xfg_classify_descs_frags",
     "xfg_classify_descs_frags_timed", "xfg_classify_socks", "xfg_socks_egress",
     "xfg_classify_socks_frags", "xfg_socks_frags_egress", "xfg_capture_descs_frags",
+    "xfg_classify_chain", "xfg_classify_descs_chain", "xfg_classify_descs_chain_timed",
 ]
 CAPTURE_HEAD_ONLY = 1        # XFG_CAPTURE_HEAD_ONLY
 SOCKS_MAX = 1024
@@ -73,6 +74,8 @@ PKT_NONE = 0xffffffff        # XFG_PKT_NONE
 EGRESS_SWAP_MACS = 1
 EGRESS_MULTIBUF = 4
 XDP_PKT_CONTD = 1
+XDP_ABORTED, XDP_DROP, XDP_PASS = 0, 1, 2
+CHAIN_PASS = 1 << XDP_PASS   # XFG_CHAIN_PASS
 # include/xdpfilter_io.h
 IO_EXPORTS = [
     "xfg_pcap_read", "xfg_host_batch_free", "xfg_pcapng_write_verdicts", "xfg_store_map_name",
@@ -117,6 +120,12 @@ class Egress(C.Structure):
 class Frags(C.Structure):
     """struct xfg_frags (xfg_classify_descs_frags)."""
     _fields_ = [("sz", C.c_size_t), ("pkt_of", C.c_void_p), ("counts", C.c_uint64 * 3)]
+
+
+class Chain(C.Structure):
+    """struct xfg_chain (xfg_classify_chain, xfg_classify_descs_chain)."""
+    _fields_ = [("sz", C.c_size_t), ("chain_mask", C.c_uint32), ("flags", C.c_uint32),
+                ("idx", C.c_void_p), ("counts", C.c_uint64 * 2)]
 
 
 class Sock(C.Structure):
@@ -221,6 +230,12 @@ def _load():
                                                C.POINTER(Frags), vp, vp]),
         "xfg_classify_descs_frags_timed": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch),
                                                      C.POINTER(Frags), vp,
+                                                     C.POINTER(C.c_double)]),
+        "xfg_classify_chain": (C.c_int, [vp, C.c_int, C.POINTER(Batch), C.POINTER(Chain), vp, vp]),
+        "xfg_classify_descs_chain": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch),
+                                               C.POINTER(Chain), vp, vp]),
+        "xfg_classify_descs_chain_timed": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch),
+                                                     C.POINTER(Chain), vp,
                                                      C.POINTER(C.c_double)]),
         "xfg_classify_xsk_host": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), C.c_uint64, vp]),
         "xfg_host_register": (C.c_int, [vp, vp, C.c_size_t]),
@@ -592,6 +607,42 @@ class Filter:
         _check(lib.xfg_classify_descs_frags_timed(self.ctx, dev, C.byref(b), C.byref(fr),
                                                   verdicts_ptr, ms), "classify_descs_frags_timed")
         return tuple(int(c) for c in fr.counts), tuple(ms)
+
+    def classify_chain(self, data_ptr, lens_ptr, count, stride, verdicts_ptr,
+                       chain_mask=CHAIN_PASS, idx_ptr=None, offsets_ptr=None, lens_u16=False,
+                       dev=0, stream=None):
+        """A chained stage over a batch (xfg_classify_chain): this context's
+        program on the frames whose verdict byte (what an earlier stage wrote
+        to verdicts_ptr) is in chain_mask; their bytes replaced, the others
+        kept.  Returns the counts (selected, not selected)."""
+        b = Batch(data_ptr, offsets_ptr, lens_ptr, count, stride, int(lens_u16))
+        ch = Chain(C.sizeof(Chain), chain_mask, 0, idx_ptr)
+        _check(lib.xfg_classify_chain(self.ctx, dev, C.byref(b), C.byref(ch), verdicts_ptr,
+                                      stream), "classify_chain")
+        return tuple(int(c) for c in ch.counts)
+
+    def classify_descs_chain(self, umem_ptr, descs_ptr, count, verdicts_ptr,
+                             chain_mask=CHAIN_PASS, idx_ptr=None, first=0, mask=0xffffffff,
+                             dev=0, stream=None):
+        """The same over a descriptor batch (xfg_classify_descs_chain).
+        Returns the counts (selected, not selected)."""
+        b = DescBatch(umem_ptr, descs_ptr, first, mask, count)
+        ch = Chain(C.sizeof(Chain), chain_mask, 0, idx_ptr)
+        _check(lib.xfg_classify_descs_chain(self.ctx, dev, C.byref(b), C.byref(ch), verdicts_ptr,
+                                            stream), "classify_descs_chain")
+        return tuple(int(c) for c in ch.counts)
+
+    def classify_descs_chain_timed(self, umem_ptr, descs_ptr, count, verdicts_ptr,
+                                   chain_mask=CHAIN_PASS, idx_ptr=None, first=0,
+                                   mask=0xffffffff, dev=0):
+        """One such call with its steps timed: (counts, (select pass ms,
+        classify ms, scatter ms)) (xfg_classify_descs_chain_timed)."""
+        b = DescBatch(umem_ptr, descs_ptr, first, mask, count)
+        ch = Chain(C.sizeof(Chain), chain_mask, 0, idx_ptr)
+        ms = (C.c_double * 3)()
+        _check(lib.xfg_classify_descs_chain_timed(self.ctx, dev, C.byref(b), C.byref(ch),
+                                                  verdicts_ptr, ms), "classify_descs_chain_timed")
+        return tuple(int(c) for c in ch.counts), tuple(ms)
 
     def host_register(self, arr: np.ndarray):
         """Pin and map a long-lived host array: the kernels read batches in it
