@@ -582,3 +582,55 @@ def test_timed_call(G):
     for x, y in zip(*got):
         np.testing.assert_array_equal(x, y)
     np.testing.assert_array_equal(got[0][0], M.merge(v_in, idx, ov[:n][idx]))
+
+
+@pytest.mark.parametrize("k", range(3), ids=["T-1", "T+1", "3T+7"])
+def test_two_threads_share_the_frags_scratch(filt, k):
+    """xfg_classify_descs_frags and xfg_classify_descs_chain size and use the
+    same library scratch under one lock.  Two threads on one context and one
+    device, 20 calls each over batches of different sizes, no pkt_of and no
+    idx passed: every call gives the verdicts and counts the same call gave
+    alone beforehand."""
+    import threading
+    from test_gpu_frags import NCHUNK, head_records, options_of
+    sizes = [T() - 1, T() + 1, 3 * T() + 7]
+    nf, nc = sizes[k], sizes[(k + 1) % 3]
+    opts, v_in = options_of(nf, "random"), verdicts_in(nc, "random")
+    dev = Bufs(filt)
+    try:
+        d_u = dev(NCHUNK * 64, np.zeros(NCHUNK * 64, np.uint8))
+        d_rx, d_vf, d_vc = dev(16 * nf, head_records(opts)), dev(nf), dev(nc)
+        s = Source(dev, nc, "ring", src=np.arange(nc) % NFRAMES)
+
+        def frags():
+            d_vf.upload(np.full(nf, 0xA5, np.uint8))
+            counts = filt.classify_descs_frags(d_u.ptr, d_rx.ptr, nf, d_vf.ptr)
+            return counts, d_vf.download(np.zeros(nf, np.uint8))
+
+        def chain():
+            d_vc.upload(v_in)
+            counts = s.chain(filt, d_vc.ptr, 1 << PASS)
+            return counts, d_vc.download(np.zeros(nc, np.uint8))
+
+        alone = [frags(), chain()]
+        assert alone[0][0][0] > 0 and alone[1][0][0] > 0
+        got = [[], []]
+
+        def worker(i, call):
+            for _ in range(20):
+                got[i].append(call())
+
+        threads = [threading.Thread(target=worker, args=(i, call), daemon=True)
+                   for i, call in enumerate((frags, chain))]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join(timeout=60)
+        assert not any(t.is_alive() for t in threads), "a thread is still in its calls"
+    finally:
+        dev.free()
+    for i in range(2):
+        assert len(got[i]) == 20
+        for counts, v in got[i]:
+            assert counts == alone[i][0]
+            np.testing.assert_array_equal(v, alone[i][1])

@@ -52,6 +52,11 @@ def random_cont(rng, n):
     return c
 
 
+# totals for the spread's lead, groups and tail: fewer records than a group, and next to tile edges
+ODD = {"odd_1": lambda: 1, "odd_3": lambda: 3, "odd_5": lambda: 5, "odd_tile_less": lambda: T() - 1,
+       "odd_tile_more": lambda: T() + 1, "odd_three_tiles": lambda: 3 * T() + 7}
+
+
 @functools.lru_cache(maxsize=None)
 def layout(name):
     """(records a socket, XDP_PKT_CONTD of every flat record), read only."""
@@ -94,6 +99,15 @@ def layout(name):
     elif name == "no_eop":
         counts = [1, 1, 2, 3, 57, 1, 63, 64, 65]
         c = np.ones(sum(counts), np.uint32)
+    elif name in ODD:
+        # two sockets; the first ends in up to five trailing records behind a whole packet
+        total = ODD[name]()
+        counts = [(total + 1) // 2, total // 2]
+        c = random_cont(rng, total)
+        c[-1] = 0
+        k = min(counts[0] - 1, 5)
+        if k:
+            c[counts[0] - k - 1], c[counts[0] - k:counts[0]] = 0, 1
     c.setflags(write=False)
     return tuple(counts), c
 
@@ -167,7 +181,7 @@ def per_socket_loop(G, g, cg, d_u, d_p, shared, flags, all_live):
 
 
 def run_round(G, traffic, name, kind, shared, no_tx=(), no_fill=(), swap=False, flat=True,
-              stream=False, all_live=False, min_packets=None):
+              stream=False, all_live=False, min_packets=None, v_off=0):
     import torch
     rules, feats, data, lens, umem, addr, oracle = traffic
     counts, cont = layout(name)
@@ -178,7 +192,7 @@ def run_round(G, traffic, name, kind, shared, no_tx=(), no_fill=(), swap=False, 
     done, pkt_of, heads, c3 = classify_model(counts, opts)
     if c3[0]:
         ov, orules, ost = oracle(name)
-        assert 0 < np.count_nonzero(ov == PASS) < c3[0]
+        assert n < 64 or 0 < np.count_nonzero(ov == PASS) < c3[0]
     else:
         ov, orules, ost = np.zeros(0, np.uint8), rules.prepared(), np.zeros((5, 2), np.uint64)
     want_v = spread(pkt_of, ov)
@@ -190,14 +204,17 @@ def run_round(G, traffic, name, kind, shared, no_tx=(), no_fill=(), swap=False, 
     c = Case(f, counts, kind, batch=batch, no_tx=no_tx, no_fill=no_fill)
     cg = Case(g, counts, kind, batch=batch, no_tx=no_tx, no_fill=no_fill)
     extra = [f.alloc(umem.nbytes), g.alloc(umem.nbytes), f.alloc(4 * n + 4), g.alloc(4 * n + 4),
-             f.alloc(16 * n)]
-    d_u, d_ug, d_p, d_pg, d_flat = extra
+             f.alloc(16 * n), f.alloc(n + 16)]
+    d_u, d_ug, d_p, d_pg, d_flat, d_vo = extra
+    # (v_off: the verdict bytes at that offset of an allocation of their own, 0xA5 around them)
+    v_ptr = d_vo.ptr + v_off if v_off else c.d_v.ptr
     try:
         for d in (d_u, d_ug):
             d.upload(umem)
         for d in (d_p, d_pg):
             d.upload(np.full(n + 1, A5_32, np.uint32))
         d_flat.upload(np.full((n, 2), A5, np.uint64))
+        d_vo.upload(np.full(n + 16, 0xA5, np.uint8))
         for k in (c, cg):
             k.d_v.upload(np.full(max(n, 16), 0xA5, np.uint8))
             k.reset_outputs()
@@ -205,9 +222,9 @@ def run_round(G, traffic, name, kind, shared, no_tx=(), no_fill=(), swap=False, 
         st = torch.cuda.Stream() if stream else None
         sp = st.cuda_stream if st else None
         # the round: one classify, one egress, nothing between them
-        got_done, got_c3 = f.classify_socks_frags(d_u.ptr, c.table(G), c.d_v.ptr, pkt_of_ptr=d_p.ptr,
+        got_done, got_c3 = f.classify_socks_frags(d_u.ptr, c.table(G), v_ptr, pkt_of_ptr=d_p.ptr,
                                                   flat_ptr=d_flat.ptr if flat else None, stream=sp)
-        f.socks_frags_egress(c.table(G), c.d_v.ptr, c.d_c.ptr, done=None if all_live else got_done,
+        f.socks_frags_egress(c.table(G), v_ptr, c.d_c.ptr, done=None if all_live else got_done,
                              fill_ptr=c.d_sfill.ptr if shared else None,
                              fill_first=c.shared.first[2], fill_mask=c.shared.mask[2],
                              umem_ptr=d_u.ptr, flags=flags, stream=sp)
@@ -218,6 +235,11 @@ def run_round(G, traffic, name, kind, shared, no_tx=(), no_fill=(), swap=False, 
         np.testing.assert_array_equal(got_done, done)
         assert got_c3 == c3 and c3[1] + c3[2] == n
         v = c.d_v.download(np.zeros(max(n, 16), np.uint8))[:n]
+        if v_off:
+            assert np.all(v == 0xA5)
+            around = d_vo.download(np.zeros(n + 16, np.uint8))
+            v = around[v_off:v_off + n]
+            assert np.all(around[:v_off] == 0xA5) and np.all(around[v_off + n:] == 0xA5)
         np.testing.assert_array_equal(v, want_v)
         p = d_p.download(np.zeros(n + 1, np.uint32))
         np.testing.assert_array_equal(p[:n], pkt_of)
@@ -311,6 +333,16 @@ ROUNDS = {
 def test_round(G, traffic, case):
     c3, out = run_round(G, traffic, **ROUNDS[case])
     assert c3[0] > 0 and c3[2] > 0               # packets, and trailing records somewhere
+
+
+@pytest.mark.parametrize("name", list(ODD))
+@pytest.mark.parametrize("v_off", [1, 2, 3])
+def test_round_with_the_verdicts_off_a_4_byte_boundary(G, traffic, name, v_off):
+    """The spread's lead bytes, whole groups and tail over all records,
+    XFG_VERDICT_NONE on the trailing ones, and nothing written around them."""
+    c3, out = run_round(G, traffic, name=name, kind="ring", shared=False, v_off=v_off)
+    n = ODD[name]()
+    assert c3[0] > 0 and c3[2] == min((n + 1) // 2 - 1, 5) and c3[1] + c3[2] == n
 
 
 @pytest.mark.parametrize("shared", [False, True], ids=["own_fill", "shared_fill"])

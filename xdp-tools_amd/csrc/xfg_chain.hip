@@ -120,11 +120,6 @@ extern "C" int xfg_launch_chain_select(const struct xfg_chain_kargs *a, unsigned
 extern "C" int xfg_launch_chain_scatter(const uint8_t *pv, const uint32_t *idx, uint8_t *verdicts,
 					uint32_t cnt, unsigned grid, void *stream)
 {
-	const uint64_t want = ((uint64_t)cnt + 255) / 256;
-	if (grid > want)
-		grid = (unsigned)want;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_chain_scatter_kernel, dim3(grid), dim3(256), 0,
-			   static_cast<hipStream_t>(stream), pv, idx, verdicts, cnt);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
+	return xfg_flat_launch(xfg_chain_scatter_kernel, ((uint64_t)cnt + 255) / 256, grid, stream, pv,
+			       idx, verdicts, cnt);
 }

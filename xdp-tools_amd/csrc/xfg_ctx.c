@@ -163,12 +163,12 @@ struct xfg_dev {
 	unsigned long long *cstatus;    /* verdict compaction, egress, capture: tile status words */
 	uint64_t cstatus_cap;
 	uint32_t *cticket;
-	/* multi-buffer descriptor batches (xfg_classify_descs_frags), one call
-	 * at a time under frags_lock: the head records, the per-packet verdicts
-	 * and, where the caller wants none, the records' packet indices.  A
-	 * chained stage (xfg_classify_chain, xfg_classify_descs_chain) has the
-	 * same three under the same lock: its selected frames' descriptors,
-	 * their verdicts and their indices */
+	/* the staged calls' scratch (staged_run()), sized there and used one
+	 * call at a time under frags_lock: for multi-buffer batches of one
+	 * socket or many (xfg_classify_descs_frags, xfg_classify_socks_frags)
+	 * the head records, the per-packet verdicts and, where the caller
+	 * passes none, the records' packet indices; for a chained stage the
+	 * selected frames' descriptors, their verdicts and their indices */
 	pthread_mutex_t frags_lock;
 	void *fr_heads;
 	uint8_t *fr_pv;
@@ -186,16 +186,17 @@ struct xfg_dev {
 	 * the device's stream; the slot's event, recorded behind the kernel that
 	 * reads the table, says when both may be written again (under d->lock;
 	 * made at first use).  One xfg_classify_socks at a time under
-	 * socks_lock: the gathered records where the caller passes no array. */
+	 * socks_lock, staged_run()'s outer lock for that call: the gathered
+	 * records where the caller passes no array, sized by its pre-pass. */
 	pthread_mutex_t socks_lock;
 	uint8_t *sk_host[SOCKS_SLOTS], *sk_dev[SOCKS_SLOTS];
 	hipEvent_t sk_done[SOCKS_SLOTS];
 	uint32_t sk_next;
 	void *sk_flat;
 	uint64_t sk_flat_bytes;
-	/* xfg_classify_socks_frags (under frags_lock, whose scratch it shares):
-	 * pinned room for its one read-back, the state words from the gave-up
-	 * word to the end of done[] */
+	/* xfg_classify_socks_frags (under frags_lock): pinned room for its one
+	 * read-back, the state words from the gave-up word to the end of
+	 * done[]; made by its pre-pass at first use */
 	unsigned long long *sf_got;
 	hipEvent_t ev_user, ev_done;    /* ordering against a caller's stream */
 };
@@ -2025,9 +2026,8 @@ int xfg_classify_timed(xfg_ctx *ctx, int dev, const struct xfg_batch *b, uint8_t
 
 /* Room for @words status words in the device's tile status buffer (d->lock
  * held, the device current): shared by every launch that goes through
- * scratch_launch(), by frags_run() and by xfg_classify_socks_frags(), which
- * run one after the other on the device's stream and each zero the words they
- * use first. */
+ * scratch_launch() or staged_run(), which run one after the other on the
+ * device's stream and each zero the words they use first. */
 static int cstatus_room(struct xfg_dev *d, uint64_t words)
 {
 	int err = 0;
@@ -2073,6 +2073,106 @@ static int scratch_launch(struct xfg_dev *d, void *stream, void *zero, size_t ze
 	err = err ? err : e2;
 fail:
 	pthread_mutex_unlock(&d->lock);
+	return err;
+}
+
+/* The calls that classify in stages (multi-buffer batches, chained stages,
+ * many sockets) are one sequence, staged_run()'s: a pre-pass over the caller's
+ * records that leaves a plain descriptor array, its counts read back, the
+ * array classified through classify(), and a post-pass that writes the
+ * verdicts back over the records by index.  What differs is this job.  @pre
+ * and @got run with d->lock held, the device current and its stream entered. */
+struct staged {
+	pthread_mutex_t *lock;  /* the call's outer lock: frags_lock, socks_lock */
+	uint64_t words;         /* status words of d->cstatus the pre-pass uses */
+	uint64_t n;             /* records fr_heads and fr_pv are sized for (0: neither) */
+	uint32_t *idx;          /* their indices: the caller's, or NULL: fr_pkt, sized too */
+	uint8_t *verdicts;      /* the caller's verdict bytes */
+	const void *umem;       /* classify(): the frames' base, */
+	const void *descs;      /* their descriptors (NULL: fr_heads; @pre may set it) */
+	uint64_t count;         /* and how many: from @got, or the caller's total */
+	uint64_t back;          /* records the post-pass writes now, by the call's rule */
+	int (*pre)(struct xfg_dev *d, struct staged *j);   /* launches on d->stream */
+	/* optional: the state words copied back and waited for (the call's one
+	 * host synchronisation), checked (-EIO), the caller's counts, @count, @back */
+	int (*got)(struct xfg_dev *d, struct staged *j);
+	/* optional (without it classify() writes @verdicts itself): fr_pv to
+	 * @verdicts by @idx, @back records of them */
+	int (*post)(const uint8_t *pv, const uint32_t *idx, uint8_t *verdicts, uint32_t n,
+		    unsigned grid, void *stream);
+	const void *arg;        /* the hooks': what the pre-pass reads, */
+	void *out;              /* the caller's struct with its counts */
+};
+
+/* the time on the device's stream since ev0 was recorded, waited for */
+static int ev_elapsed(struct xfg_dev *d, double *ms)
+{
+	float t = 0;
+	int err = hip_err(hipEventRecord(d->ev1, d->stream));
+	if (!err && !(err = hip_err(hipEventSynchronize(d->ev1))))
+		err = hip_err(hipEventElapsedTime(&t, d->ev0, d->ev1));
+	*ms = t;
+	return err;
+}
+
+/* All of a staged call on the device's own stream, after @stream's earlier
+ * work and before its later.  The outer lock keeps a second caller off the
+ * scratch between the steps: d->lock itself is released around classify(),
+ * which takes it.  @ms (the timed entry points): the three steps' durations,
+ * each between two events and waited for.  Once the device's stream was
+ * entered it is left too, whatever failed -- a hook, classify(), making the
+ * device current again behind it (-EIO, unless classify() failed) -- with
+ * d->lock held and the caller's stream behind whatever was queued; the first
+ * error is returned. */
+static int staged_run(xfg_ctx *ctx, int dev, struct staged *j, void *stream, double *ms)
+{
+	struct xfg_dev *d = &ctx->dev[dev];
+	int err = 0, entered = 0;
+	pthread_mutex_lock(j->lock);
+	pthread_mutex_lock(&d->lock);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if ((err = cstatus_room(d, j->words)) ||
+	    (err = scratch(d, &d->fr_heads, &d->fr_heads_bytes, j->n * 16)) ||
+	    (err = scratch(d, (void **)&d->fr_pv, &d->fr_pv_bytes, j->n)) ||
+	    (!j->idx && (err = scratch(d, (void **)&d->fr_pkt, &d->fr_pkt_bytes, j->n * 4))))
+		goto fail;
+	if (!j->idx)
+		j->idx = d->fr_pkt;
+	if ((err = stream_enter(d, stream)))
+		goto fail;
+	entered = 1;
+	if (ms)
+		HIPCHK(hipEventRecord(d->ev0, d->stream));
+	if ((err = j->pre(d, j)) || (ms && (err = ev_elapsed(d, &ms[0]))) ||
+	    (j->got && (err = j->got(d, j))))
+		goto fail;
+	if (j->count) {
+		const struct xfg_desc_batch hb = { j->umem, j->descs ? j->descs : d->fr_heads, 0,
+						   0xffffffffu, j->count };
+		uint8_t *pv = j->post ? d->fr_pv : j->verdicts;
+		pthread_mutex_unlock(&d->lock);
+		err = classify(ctx, dev, NULL, &hb, pv, NULL, 1, ms ? &ms[1] : NULL);
+		pthread_mutex_lock(&d->lock);
+		if (hipSetDevice(d->ordinal) != hipSuccess)
+			err = err ? err : -EIO;
+		if (err)
+			goto fail;
+	}
+	if (j->post && j->back) {
+		if (ms)
+			HIPCHK(hipEventRecord(d->ev0, d->stream));
+		if ((err = j->post(d->fr_pv, j->idx, j->verdicts, (uint32_t)j->back, (unsigned)d->ncu * 8,
+				   d->stream)) ||
+		    (ms && (err = ev_elapsed(d, &ms[2]))))
+			goto fail;
+	}
+fail:
+	if (entered) {
+		const int e2 = stream_leave(d, stream);
+		err = err ? err : e2;
+	}
+	pthread_mutex_unlock(&d->lock);
+	pthread_mutex_unlock(j->lock);
 	return err;
 }
 
@@ -2161,16 +2261,37 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e, const uin
 			      XFG_EGRESS_STATE_WORDS(e->count), egress_go, &a);
 }
 
-/* Multi-buffer descriptor batches (include/xdpfilter_gpu.h): the head pass
- * over the records, its counts read back (the call's one host
- * synchronisation: the classify launch is planned from the packet count), the
- * packets' head records classified as a plain descriptor array through
- * classify(), and their verdicts spread over the records.  All of it on the
- * device's own stream, after @stream's earlier work and before its later;
- * frags_lock keeps a second caller off the head and verdict scratch between
- * the steps (d->lock itself is released for classify(), which takes it).
- * @ms (the timed entry point): the three steps' durations, each between two
- * events and waited for. */
+/* Multi-buffer descriptor batches (include/xdpfilter_gpu.h), a staged call
+ * under frags_lock: the head pass over the records, its packet and record
+ * counts read back (the classify launch is planned from the packet count), the
+ * packets' head records classified, and their verdicts spread over the records
+ * of complete packets, if there are any. */
+static int frags_pre(struct xfg_dev *d, struct staged *j)
+{
+	const struct xfg_desc_batch *db = j->arg;
+	const struct xfg_frags_kargs a = {
+		.rx = db->descs, .pkt_of = j->idx, .heads = d->fr_heads, .state = d->cstatus,
+		.first = db->first, .mask = db->mask, .n = (uint32_t)j->n,
+	};
+	/* (four workgroups a CU: all of them resident) */
+	return xfg_launch_frags_heads(&a, (unsigned)d->ncu * 4, d->stream);
+}
+
+static int frags_got(struct xfg_dev *d, struct staged *j)
+{
+	struct xfg_frags *fr = j->out;
+	unsigned long long got[2] = { 0, 0 };
+	const int err = dev_read(d, got, d->cstatus + 2, sizeof(got));
+	if (err)
+		return err;
+	if (got[0] > j->n || got[1] > j->n || (got[0] != 0) != (got[1] != 0))
+		return -EIO;
+	fr->counts[0] = j->count = got[0];
+	fr->counts[1] = j->back = got[1];
+	fr->counts[2] = j->n - got[1];
+	return 0;
+}
+
 static int frags_run(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db, struct xfg_frags *fr,
 		     uint8_t *verdicts, void *stream, double *ms)
 {
@@ -2185,78 +2306,13 @@ static int frags_run(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db, str
 		ms[0] = ms[1] = ms[2] = 0;
 	if (err)   /* an empty batch */
 		return 0;
-	struct xfg_dev *d = &ctx->dev[dev];
-	const uint64_t n = db->count;
-	unsigned long long got[2] = { 0, 0 };
-	float t = 0;
-	int entered = 0;
-	pthread_mutex_lock(&d->frags_lock);
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if ((err = cstatus_room(d, XFG_FRAGS_STATE_WORDS(n))) ||
-	    (err = scratch(d, &d->fr_heads, &d->fr_heads_bytes, n * 16)) ||
-	    (err = scratch(d, (void **)&d->fr_pv, &d->fr_pv_bytes, n)) ||
-	    (!fr->pkt_of && (err = scratch(d, (void **)&d->fr_pkt, &d->fr_pkt_bytes, n * 4))))
-		goto fail;
-	uint32_t *pkt_of = fr->pkt_of ? fr->pkt_of : d->fr_pkt;
-	struct xfg_frags_kargs a = {
-		.rx = db->descs, .pkt_of = pkt_of, .heads = d->fr_heads, .state = d->cstatus,
-		.first = db->first, .mask = db->mask, .n = (uint32_t)n,
+	struct staged j = {
+		.lock = &ctx->dev[dev].frags_lock, .words = XFG_FRAGS_STATE_WORDS(db->count),
+		.n = db->count, .idx = fr->pkt_of, .verdicts = verdicts, .umem = db->umem,
+		.pre = frags_pre, .got = frags_got, .post = xfg_launch_frags_spread,
+		.arg = db, .out = fr,
 	};
-	if ((err = stream_enter(d, stream)))
-		goto fail;
-	entered = 1;
-	if (ms)
-		HIPCHK(hipEventRecord(d->ev0, d->stream));
-	/* (four workgroups a CU: all of them resident) */
-	if ((err = xfg_launch_frags_heads(&a, (unsigned)d->ncu * 4, d->stream)))
-		goto fail;
-	if (ms)
-		HIPCHK(hipEventRecord(d->ev1, d->stream));
-	HIPCHK(hipMemcpyAsync(got, d->cstatus + 2, sizeof(got), hipMemcpyDeviceToHost, d->stream));
-	HIPCHK(hipStreamSynchronize(d->stream));
-	if (ms) {
-		HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-		ms[0] = t;
-	}
-	if (got[0] > n || got[1] > n || (got[0] != 0) != (got[1] != 0)) {
-		err = -EIO;
-		goto fail;
-	}
-	fr->counts[0] = got[0];
-	fr->counts[1] = got[1];
-	fr->counts[2] = n - got[1];
-	pthread_mutex_unlock(&d->lock);
-	if (got[0]) {
-		const struct xfg_desc_batch hb = { db->umem, d->fr_heads, 0, 0xffffffffu, got[0] };
-		if ((err = classify(ctx, dev, NULL, &hb, d->fr_pv, NULL, 1, ms ? &ms[1] : NULL)))
-			goto leave;
-	}
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (got[1]) {
-		if (ms)
-			HIPCHK(hipEventRecord(d->ev0, d->stream));
-		if ((err = xfg_launch_frags_spread(d->fr_pv, pkt_of, verdicts, (uint32_t)got[1],
-						   (unsigned)d->ncu * 8, d->stream)))
-			goto fail;
-		if (ms) {
-			HIPCHK(hipEventRecord(d->ev1, d->stream));
-			HIPCHK(hipEventSynchronize(d->ev1));
-			HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-			ms[2] = t;
-		}
-	}
-fail:
-	/* (also after an error: the caller's stream behind what was queued) */
-	if (entered) {
-		const int e2 = stream_leave(d, stream);
-		err = err ? err : e2;
-	}
-	pthread_mutex_unlock(&d->lock);
-leave:
-	pthread_mutex_unlock(&d->frags_lock);
-	return err;
+	return staged_run(ctx, dev, &j, stream, ms);
 }
 
 int xfg_classify_descs_frags(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
@@ -2273,16 +2329,38 @@ int xfg_classify_descs_frags_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_
 	return frags_run(ctx, dev, db, fr, verdicts, NULL, ms);
 }
 
-/* A chained stage (include/xdpfilter_gpu.h) over @b or over @db: frags_run()'s
- * sequence with the select pass in the head pass's place -- the pass over the
- * earlier stage's verdict bytes, the selected count read back (the call's one
- * host synchronisation: the classify launch is planned from it), the selected
- * frames classified as a plain descriptor array over the batch's bytes through
- * classify(), and their verdicts scattered to the frames' own bytes.  On the
- * device's own stream between @stream's earlier and later work, under
- * frags_lock, whose scratch it uses (the heads' room for the descriptors, the
- * packet indices' for idx).  The argument checks come first and the empty
- * batch next, neither needing a device. */
+/* A chained stage (include/xdpfilter_gpu.h) over @b or over @db, a staged
+ * call: the select pass over the earlier stage's verdict bytes, the selected
+ * count read back (the classify launch is planned from it), the selected
+ * frames classified as a plain descriptor array over the batch's bytes, and
+ * their verdicts scattered to the frames' own bytes, if any was selected.
+ * Under frags_lock, whose scratch it uses (the heads' room for the
+ * descriptors, the packet indices' for idx).  The argument checks come first
+ * and the empty batch next, neither needing a device. */
+static int chain_pre(struct xfg_dev *d, struct staged *j)
+{
+	struct xfg_chain_kargs a = *(const struct xfg_chain_kargs *)j->arg;   /* (the frames) */
+	a.idx = j->idx;
+	a.sel = d->fr_heads;
+	a.state = d->cstatus;
+	/* (four workgroups a CU: all of them resident) */
+	return xfg_launch_chain_select(&a, (unsigned)d->ncu * 4, d->stream);
+}
+
+static int chain_got(struct xfg_dev *d, struct staged *j)
+{
+	struct xfg_chain *ch = j->out;
+	unsigned long long got = 0;
+	const int err = dev_read(d, &got, d->cstatus + 2, sizeof(got));
+	if (err)
+		return err;
+	if (got > j->n)
+		return -EIO;
+	ch->counts[0] = j->count = j->back = got;
+	ch->counts[1] = j->n - got;
+	return 0;
+}
+
 static int chain_run(xfg_ctx *ctx, int dev, const struct xfg_batch *b,
 		     const struct xfg_desc_batch *db, struct xfg_chain *ch, uint8_t *verdicts,
 		     void *stream, double *ms)
@@ -2309,22 +2387,8 @@ static int chain_run(xfg_ctx *ctx, int dev, const struct xfg_batch *b,
 	ch->counts[1] = n;
 	if (!ch->chain_mask)
 		return 0;
-	struct xfg_dev *d = &ctx->dev[dev];
-	unsigned long long got = 0;
-	float t = 0;
-	int entered = 0;
-	pthread_mutex_lock(&d->frags_lock);
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if ((err = cstatus_room(d, XFG_CHAIN_STATE_WORDS(n))) ||
-	    (err = scratch(d, &d->fr_heads, &d->fr_heads_bytes, n * 16)) ||
-	    (err = scratch(d, (void **)&d->fr_pv, &d->fr_pv_bytes, n)) ||
-	    (!ch->idx && (err = scratch(d, (void **)&d->fr_pkt, &d->fr_pkt_bytes, n * 4))))
-		goto fail;
-	uint32_t *idx = ch->idx ? ch->idx : d->fr_pkt;
 	struct xfg_chain_kargs a = {
-		.verdicts = verdicts, .idx = idx, .sel = d->fr_heads, .state = d->cstatus,
-		.n = (uint32_t)n, .chain_mask = ch->chain_mask,
+		.verdicts = verdicts, .n = (uint32_t)n, .chain_mask = ch->chain_mask,
 	};
 	if (db) {
 		a.descs = db->descs;
@@ -2337,59 +2401,13 @@ static int chain_run(xfg_ctx *ctx, int dev, const struct xfg_batch *b,
 		a.stride = b->stride;
 		a.form = b->lens_u16 ? XFG_CHAIN_F_LENS_U16 : 0;
 	}
-	if ((err = stream_enter(d, stream)))
-		goto fail;
-	entered = 1;
-	if (ms)
-		HIPCHK(hipEventRecord(d->ev0, d->stream));
-	/* (four workgroups a CU: all of them resident) */
-	if ((err = xfg_launch_chain_select(&a, (unsigned)d->ncu * 4, d->stream)))
-		goto fail;
-	if (ms)
-		HIPCHK(hipEventRecord(d->ev1, d->stream));
-	HIPCHK(hipMemcpyAsync(&got, d->cstatus + 2, sizeof(got), hipMemcpyDeviceToHost, d->stream));
-	HIPCHK(hipStreamSynchronize(d->stream));
-	if (ms) {
-		HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-		ms[0] = t;
-	}
-	if (got > n) {
-		err = -EIO;
-		goto fail;
-	}
-	ch->counts[0] = got;
-	ch->counts[1] = n - got;
-	if (got) {
-		const struct xfg_desc_batch sb = { db ? db->umem : b->data, d->fr_heads, 0, 0xffffffffu,
-						   got };
-		/* (classify() takes d->lock itself) */
-		pthread_mutex_unlock(&d->lock);
-		err = classify(ctx, dev, NULL, &sb, d->fr_pv, NULL, 1, ms ? &ms[1] : NULL);
-		pthread_mutex_lock(&d->lock);
-		if (err)
-			goto fail;
-		HIPCHK(hipSetDevice(d->ordinal));
-		if (ms)
-			HIPCHK(hipEventRecord(d->ev0, d->stream));
-		if ((err = xfg_launch_chain_scatter(d->fr_pv, idx, verdicts, (uint32_t)got,
-						    (unsigned)d->ncu * 8, d->stream)))
-			goto fail;
-		if (ms) {
-			HIPCHK(hipEventRecord(d->ev1, d->stream));
-			HIPCHK(hipEventSynchronize(d->ev1));
-			HIPCHK(hipEventElapsedTime(&t, d->ev0, d->ev1));
-			ms[2] = t;
-		}
-	}
-fail:
-	/* (also after an error: the caller's stream behind what was queued) */
-	if (entered) {
-		const int e2 = stream_leave(d, stream);
-		err = err ? err : e2;
-	}
-	pthread_mutex_unlock(&d->lock);
-	pthread_mutex_unlock(&d->frags_lock);
-	return err;
+	struct staged j = {
+		.lock = &ctx->dev[dev].frags_lock, .words = XFG_CHAIN_STATE_WORDS(n), .n = n,
+		.idx = ch->idx, .verdicts = verdicts, .umem = db ? db->umem : b->data,
+		.pre = chain_pre, .got = chain_got, .post = xfg_launch_chain_scatter,
+		.arg = &a, .out = ch,
+	};
+	return staged_run(ctx, dev, &j, stream, ms);
 }
 
 int xfg_classify_chain(xfg_ctx *ctx, int dev, const struct xfg_batch *b, struct xfg_chain *ch,
@@ -2490,23 +2508,40 @@ fail:
 	return err;
 }
 
-/* ... behind that kernel (or behind the copy alone, if its launch failed). */
-static int socks_table_done(struct xfg_dev *d, int slot)
+/* ... behind that kernel (or behind the copy alone, if its launch failed:
+ * @err, which stands). */
+static int socks_table_done(struct xfg_dev *d, int slot, int err)
 {
-	return hip_err(hipEventRecord(d->sk_done[slot], d->stream));
+	const int e1 = hip_err(hipEventRecord(d->sk_done[slot], d->stream));
+	return err ? err : e1;
 }
 
-/* One classify for the sockets' batches: the gather kernel, then classify()
- * over the flat array as xfg_classify_descs runs it.  All of it on the
- * device's own stream, after @stream's earlier work and before its later, with
- * no host synchronisation; socks_lock keeps a second caller off the flat
- * scratch between the two steps (d->lock itself is released for classify(),
- * which takes it), as frags_lock does in frags_run(). */
+/* One classify for the sockets' batches, a staged call under socks_lock with
+ * nothing read back, so no host synchronisation, and no post-pass: the gather
+ * kernel into the caller's flat array or the library's (sized with the stream
+ * entered, as scratch_launch()'s launch functions size theirs), then the flat
+ * array classified as xfg_classify_descs runs it, into the caller's verdicts. */
+static int socks_pre(struct xfg_dev *d, struct staged *j)
+{
+	const struct xfg_socks *sk = j->arg;
+	struct xfg_socks_gather_kargs a = {
+		.flat = sk->flat, .n = (uint32_t)j->count, .nsocks = sk->nsocks,
+	};
+	int err, slot = -1;
+	if (!a.flat && (err = scratch(d, &d->sk_flat, &d->sk_flat_bytes, j->count * 16)))
+		return err;
+	j->descs = a.flat = a.flat ? a.flat : d->sk_flat;
+	if ((err = socks_table(d, sk, &slot, &a.ents, &a.base, NULL, NULL)))
+		return err;
+	err = xfg_launch_socks_gather(&a, (unsigned)d->ncu * 8, d->stream);
+	return socks_table_done(d, slot, err);
+}
+
 int xfg_classify_socks(xfg_ctx *ctx, int dev, const struct xfg_socks *sk, uint8_t *verdicts,
 		       void *stream)
 {
 	uint64_t total = 0;
-	int err, entered = 0, slot = -1;
+	int err;
 	if (!ctx)
 		return -EINVAL;
 	if ((err = socks_check(sk, &total)))
@@ -2517,39 +2552,12 @@ int xfg_classify_socks(xfg_ctx *ctx, int dev, const struct xfg_socks *sk, uint8_
 		return err;
 	if (!total)
 		return 0;
-	struct xfg_dev *d = &ctx->dev[dev];
-	pthread_mutex_lock(&d->socks_lock);
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!sk->flat && (err = scratch(d, &d->sk_flat, &d->sk_flat_bytes, total * 16)))
-		goto fail;
-	struct xfg_socks_gather_kargs a = {
-		.flat = sk->flat ? sk->flat : d->sk_flat, .n = (uint32_t)total, .nsocks = sk->nsocks,
+	/* (n = 0: nothing of fr_* is sized) */
+	struct staged j = {
+		.lock = &ctx->dev[dev].socks_lock, .verdicts = verdicts, .umem = sk->umem,
+		.count = total, .pre = socks_pre, .arg = sk,
 	};
-	if ((err = stream_enter(d, stream)))
-		goto fail;
-	entered = 1;
-	if ((err = socks_table(d, sk, &slot, &a.ents, &a.base, NULL, NULL)))
-		goto fail;
-	err = xfg_launch_socks_gather(&a, (unsigned)d->ncu * 8, d->stream);
-	const int e1 = socks_table_done(d, slot);
-	if ((err = err ? err : e1))
-		goto fail;
-	pthread_mutex_unlock(&d->lock);
-	const struct xfg_desc_batch flat = { sk->umem, a.flat, 0, 0xffffffffu, total };
-	err = classify(ctx, dev, NULL, &flat, verdicts, NULL, 1, NULL);
-	pthread_mutex_lock(&d->lock);
-	if (hipSetDevice(d->ordinal) != hipSuccess)
-		err = err ? err : -EIO;
-fail:
-	/* (also after an error: the caller's stream behind what was queued) */
-	if (entered) {
-		const int e2 = stream_leave(d, stream);
-		err = err ? err : e2;
-	}
-	pthread_mutex_unlock(&d->lock);
-	pthread_mutex_unlock(&d->socks_lock);
-	return err;
+	return staged_run(ctx, dev, &j, stream, NULL);
 }
 
 /* What both egress calls check beyond socks_check(): @flags_ok the flags the
@@ -2614,8 +2622,7 @@ static int socks_egress_go(struct xfg_dev *d, unsigned grid, void *arg)
 		};
 		err = xfg_launch_socks_egress(&b, grid, d->stream);
 	}
-	const int e1 = socks_table_done(d, slot);
-	return err ? err : e1;
+	return socks_table_done(d, slot, err);
 }
 
 static int socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
@@ -2657,20 +2664,64 @@ int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 	return socks_egress(ctx, dev, sk, e, NULL, verdicts, stream, 0);
 }
 
-/* Multi-buffer batches of many sockets (include/xdpfilter_gpu.h): the done
- * pass and the head pass over all the sockets' records, the state words with
- * done[] and the packet count read back (the call's one host synchronisation,
- * as in frags_run()), the complete packets' heads classified as a plain
- * descriptor array through classify(), and the verdicts spread over all the
- * records.  All of it on the device's own stream, after @stream's earlier work
- * and before its later.  The head, verdict and packet-index scratch is
- * frags_run()'s, so frags_lock keeps a second caller of either off it between
- * the steps (d->lock itself is released for classify(), which takes it). */
+/* Multi-buffer batches of many sockets (include/xdpfilter_gpu.h), a staged
+ * call: the done pass and the head pass over all the sockets' records, the
+ * state words with done[] and the packet count read back through pinned
+ * memory, the complete packets' heads classified, and the verdicts spread over
+ * all the records, always (a trailing record gets XFG_VERDICT_NONE).  The
+ * head, verdict and packet-index scratch is frags_run()'s, so frags_lock keeps
+ * a second caller of either off it. */
+static int socks_frags_pre(struct xfg_dev *d, struct staged *j)
+{
+	const struct xfg_socks *sk = j->arg;
+	struct xfg_socks_frags_kargs a = {
+		.flat = sk->flat, .pkt_of = j->idx, .heads = d->fr_heads, .state = d->cstatus,
+		.n = (uint32_t)j->n, .nsocks = sk->nsocks,
+	};
+	const size_t got_bytes = (XFG_SOCKS_FRAGS_DONE_WORD + XFG_SOCKS_FRAGS_DONE_WORDS(XFG_SOCKS_MAX)) * 8;
+	int err, slot = -1;
+	if (!d->sf_got &&
+	    (err = hip_err(hipHostMalloc((void **)&d->sf_got, got_bytes, hipHostMallocDefault))))
+		return err;
+	if ((err = socks_table(d, sk, &slot, &a.ents, &a.base, NULL, NULL)))
+		return err;
+	/* (four workgroups a CU: all of them resident) */
+	err = xfg_launch_socks_frags_heads(&a, (unsigned)d->ncu * 4, d->stream);
+	return socks_table_done(d, slot, err);
+}
+
+static int socks_frags_got(struct xfg_dev *d, struct staged *j)
+{
+	const struct xfg_socks *sk = j->arg;
+	struct xfg_socks_frags *fr = j->out;
+	/* state words 1 .. 3 and done[] behind them */
+	const uint64_t ngot = XFG_SOCKS_FRAGS_DONE_WORD - 1 + XFG_SOCKS_FRAGS_DONE_WORDS(sk->nsocks);
+	const uint32_t *got_done = (const uint32_t *)(d->sf_got + XFG_SOCKS_FRAGS_DONE_WORD - 1);
+	uint64_t recs = 0;
+	const int err = dev_read(d, d->sf_got, d->cstatus + 1, ngot * 8);
+	if (err)
+		return err;
+	const uint64_t packets = d->sf_got[1];
+	for (uint32_t s = 0; s < sk->nsocks; s++) {
+		if (got_done[s] > sk->socks[s].count)
+			d->sf_got[0] = 1;
+		recs += got_done[s];
+	}
+	/* (word 1: a look-back gave up) */
+	if (d->sf_got[0] || packets > recs || (packets != 0) != (recs != 0))
+		return -EIO;
+	memcpy(fr->done, got_done, (size_t)sk->nsocks * 4);
+	fr->counts[0] = j->count = packets;
+	fr->counts[1] = recs;
+	fr->counts[2] = j->n - recs;
+	return 0;
+}
+
 int xfg_classify_socks_frags(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 			     struct xfg_socks_frags *fr, uint8_t *verdicts, void *stream)
 {
 	uint64_t total = 0;
-	int err, entered = 0, slot = -1;
+	int err;
 	if (!ctx)
 		return -EINVAL;
 	if ((err = socks_check(sk, &total)))
@@ -2685,75 +2736,14 @@ int xfg_classify_socks_frags(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 	fr->counts[0] = fr->counts[1] = fr->counts[2] = 0;
 	if (!total)
 		return 0;
-	struct xfg_dev *d = &ctx->dev[dev];
-	/* the read-back: state words 1 .. 3 and done[] behind them */
-	const uint64_t ngot = XFG_SOCKS_FRAGS_DONE_WORD - 1 + XFG_SOCKS_FRAGS_DONE_WORDS(sk->nsocks);
-	uint64_t packets = 0, recs = 0;
-	pthread_mutex_lock(&d->frags_lock);
-	pthread_mutex_lock(&d->lock);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!d->sf_got)
-		HIPCHK(hipHostMalloc((void **)&d->sf_got,
-				     (XFG_SOCKS_FRAGS_DONE_WORD + XFG_SOCKS_FRAGS_DONE_WORDS(XFG_SOCKS_MAX)) * 8,
-				     hipHostMallocDefault));
-	if ((err = cstatus_room(d, XFG_SOCKS_FRAGS_STATE_WORDS(total, sk->nsocks))) ||
-	    (err = scratch(d, &d->fr_heads, &d->fr_heads_bytes, total * 16)) ||
-	    (err = scratch(d, (void **)&d->fr_pv, &d->fr_pv_bytes, total)) ||
-	    (!fr->pkt_of && (err = scratch(d, (void **)&d->fr_pkt, &d->fr_pkt_bytes, total * 4))))
-		goto fail;
-	uint32_t *pkt_of = fr->pkt_of ? fr->pkt_of : d->fr_pkt;
-	struct xfg_socks_frags_kargs a = {
-		.flat = sk->flat, .pkt_of = pkt_of, .heads = d->fr_heads, .state = d->cstatus,
-		.n = (uint32_t)total, .nsocks = sk->nsocks,
+	struct staged j = {
+		.lock = &ctx->dev[dev].frags_lock,
+		.words = XFG_SOCKS_FRAGS_STATE_WORDS(total, sk->nsocks), .n = total, .idx = fr->pkt_of,
+		.verdicts = verdicts, .umem = sk->umem, .back = total,
+		.pre = socks_frags_pre, .got = socks_frags_got, .post = xfg_launch_socks_frags_spread,
+		.arg = sk, .out = fr,
 	};
-	if ((err = stream_enter(d, stream)))
-		goto fail;
-	entered = 1;
-	if ((err = socks_table(d, sk, &slot, &a.ents, &a.base, NULL, NULL)))
-		goto fail;
-	/* (four workgroups a CU: all of them resident) */
-	err = xfg_launch_socks_frags_heads(&a, (unsigned)d->ncu * 4, d->stream);
-	const int e1 = socks_table_done(d, slot);
-	if ((err = err ? err : e1))
-		goto fail;
-	HIPCHK(hipMemcpyAsync(d->sf_got, d->cstatus + 1, ngot * 8, hipMemcpyDeviceToHost, d->stream));
-	HIPCHK(hipStreamSynchronize(d->stream));
-	const uint32_t *got_done = (const uint32_t *)(d->sf_got + XFG_SOCKS_FRAGS_DONE_WORD - 1);
-	packets = d->sf_got[1];
-	for (uint32_t s = 0; s < sk->nsocks; s++) {
-		if (got_done[s] > sk->socks[s].count)
-			d->sf_got[0] = 1;
-		recs += got_done[s];
-	}
-	/* (word 1: a look-back gave up) */
-	if (d->sf_got[0] || packets > recs || (packets != 0) != (recs != 0)) {
-		err = -EIO;
-		goto fail;
-	}
-	memcpy(fr->done, got_done, (size_t)sk->nsocks * 4);
-	fr->counts[0] = packets;
-	fr->counts[1] = recs;
-	fr->counts[2] = total - recs;
-	pthread_mutex_unlock(&d->lock);
-	if (packets) {
-		const struct xfg_desc_batch hb = { sk->umem, d->fr_heads, 0, 0xffffffffu, packets };
-		err = classify(ctx, dev, NULL, &hb, d->fr_pv, NULL, 1, NULL);
-	}
-	pthread_mutex_lock(&d->lock);
-	if (hipSetDevice(d->ordinal) != hipSuccess)
-		err = err ? err : -EIO;
-	if (!err)
-		err = xfg_launch_socks_frags_spread(d->fr_pv, pkt_of, verdicts, (uint32_t)total,
-						    (unsigned)d->ncu * 8, d->stream);
-fail:
-	/* (also after an error: the caller's stream behind what was queued) */
-	if (entered) {
-		const int e2 = stream_leave(d, stream);
-		err = err ? err : e2;
-	}
-	pthread_mutex_unlock(&d->lock);
-	pthread_mutex_unlock(&d->frags_lock);
-	return err;
+	return staged_run(ctx, dev, &j, stream, NULL);
 }
 
 /* ... and their egress */

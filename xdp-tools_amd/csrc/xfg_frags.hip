@@ -26,6 +26,24 @@
 namespace {
 typedef u32x4 __attribute__((aligned(4))) u32x4_a4;
 typedef const __attribute__((address_space(1))) u32x4_a4 fr_gidx4;
+
+template <bool NONE>
+__device__ __forceinline__ uint32_t fr_verdict(const uint8_t *pv, uint32_t p)
+{
+	return NONE && p == XFG_SOCKS_FRAGS_PKT_NONE ? XFG_SOCKS_FRAGS_VERDICT_NONE : pv[p];
+}
+
+// The launch of a kernel that waits for nothing, 256 threads a workgroup, on
+// @stream: a grid of at most @want workgroups (the work's).
+template <class K, class... A>
+int xfg_flat_launch(K kernel, uint64_t want, unsigned grid, void *stream, const A &...args)
+{
+	if (grid > want)
+		grid = (unsigned)want;
+	(void)hipGetLastError();
+	hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), args...);
+	return hipGetLastError() == hipSuccess ? 0 : -5;
+}
 }  // namespace
 
 static_assert(SC_LANES * SC_PASSES == XFG_FRAGS_TILE, "tile shape");
@@ -104,6 +122,10 @@ __global__ __launch_bounds__(SC_LANES) void xfg_frags_heads_kernel(const xfg_fra
 	}
 }
 
+// (NONE: xfg_classify_socks_frags()'s spread over all records, where a record
+// of a trailing incomplete packet carries XFG_PKT_NONE and gets
+// XFG_VERDICT_NONE)
+template <bool NONE>
 __global__ __launch_bounds__(256) void xfg_frags_spread_kernel(
 	const uint8_t *__restrict__ pv, const uint32_t *__restrict__ pkt_of,
 	uint8_t *__restrict__ verdicts, uint32_t done)
@@ -118,14 +140,15 @@ __global__ __launch_bounds__(256) void xfg_frags_spread_kernel(
 		const u32x4 p = __builtin_nontemporal_load(reinterpret_cast<fr_gidx4 *>(
 			(uint64_t)(uintptr_t)pkt_of + 4ull * i));
 		*reinterpret_cast<uint32_t *>(verdicts + i) =
-			pv[p.x] | (uint32_t)pv[p.y] << 8 | (uint32_t)pv[p.z] << 16 | (uint32_t)pv[p.w] << 24;
+			fr_verdict<NONE>(pv, p.x) | fr_verdict<NONE>(pv, p.y) << 8 |
+			fr_verdict<NONE>(pv, p.z) << 16 | fr_verdict<NONE>(pv, p.w) << 24;
 	}
 	// the bytes before the first 4-byte boundary and past the last whole group
 	const uint32_t rest = lead + 4 * groups;
 	if (tid < lead)
-		verdicts[tid] = pv[pkt_of[tid]];
+		verdicts[tid] = (uint8_t)fr_verdict<NONE>(pv, pkt_of[tid]);
 	if (tid < done - rest)
-		verdicts[rest + tid] = pv[pkt_of[rest + tid]];
+		verdicts[rest + tid] = (uint8_t)fr_verdict<NONE>(pv, pkt_of[rest + tid]);
 }
 
 extern "C" int xfg_launch_frags_heads(const struct xfg_frags_kargs *a, unsigned grid, void *stream)
@@ -137,12 +160,6 @@ extern "C" int xfg_launch_frags_heads(const struct xfg_frags_kargs *a, unsigned 
 extern "C" int xfg_launch_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *verdicts,
 				       uint32_t done, unsigned grid, void *stream)
 {
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	const uint64_t want = ((uint64_t)done / 4 + 255) / 256 + 1;
-	if (grid > want)
-		grid = (unsigned)want;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_frags_spread_kernel, dim3(grid), dim3(256), 0, s, pv, pkt_of, verdicts,
-			   done);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
+	return xfg_flat_launch(xfg_frags_spread_kernel<false>, ((uint64_t)done / 4 + 255) / 256 + 1, grid,
+			       stream, pv, pkt_of, verdicts, done);
 }

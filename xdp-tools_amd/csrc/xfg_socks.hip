@@ -245,13 +245,7 @@ __global__ __launch_bounds__(SC_LANES) void xfg_socks_egress_kernel(const xfg_so
 extern "C" int xfg_launch_socks_gather(const struct xfg_socks_gather_kargs *a, unsigned grid,
 				       void *stream)
 {
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	const uint64_t want = ((uint64_t)a->n + 255) / 256;
-	if (grid > want)
-		grid = (unsigned)want;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_socks_gather_kernel, dim3(grid), dim3(256), 0, s, *a);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
+	return xfg_flat_launch(xfg_socks_gather_kernel, ((uint64_t)a->n + 255) / 256, grid, stream, *a);
 }
 
 extern "C" int xfg_launch_socks_egress(const struct xfg_socks_kargs *a, unsigned grid, void *stream)

@@ -32,7 +32,7 @@
 // XFG_PKT_NONE.  The last tile leaves the packet count in state word 2.
 //
 // Spread: verdicts[i] = pv[pkt_of[i]], or XFG_VERDICT_NONE where pkt_of[i] is
-// XFG_PKT_NONE, over all records, four a lane as xfg_frags_spread_kernel.
+// XFG_PKT_NONE, over all records: xfg_frags_spread_kernel<true> (xfg_frags.hip).
 //
 // Egress: xfg_socks_egress_kernel over the live records.  A record is live if
 // i - base[s] < done[s] (done[] and its prefix sums dbase[] in LDS beside the
@@ -54,7 +54,6 @@
 
 namespace {
 constexpr uint32_t SF_PKT_NONE = XFG_SOCKS_FRAGS_PKT_NONE;
-constexpr uint32_t SF_VERDICT_NONE = XFG_SOCKS_FRAGS_VERDICT_NONE;
 
 // socket s's RX record j (16 bytes), and its options alone
 __device__ __forceinline__ u32x4 sf_rec(const u32x4 rx, uint32_t j)
@@ -67,11 +66,6 @@ __device__ __forceinline__ uint32_t sf_opts(const u32x4 rx, uint32_t j)
 {
 	return *reinterpret_cast<gu32 *>(((uint64_t)rx.y << 32 | rx.x) +
 					    16ull * ((rx.z + j) & rx.w) + 12);
-}
-
-__device__ __forceinline__ uint32_t sf_verdict(const uint8_t *pv, uint32_t p)
-{
-	return p == SF_PKT_NONE ? SF_VERDICT_NONE : pv[p];
 }
 }  // namespace
 
@@ -192,31 +186,6 @@ __global__ __launch_bounds__(SC_LANES) void xfg_socks_frags_heads_kernel(const x
 		}
 		__syncthreads();   // s_cnt / the ticket's word reused
 	}
-}
-
-__global__ __launch_bounds__(256) void xfg_socks_frags_spread_kernel(
-	const uint8_t *__restrict__ pv, const uint32_t *__restrict__ pkt_of,
-	uint8_t *__restrict__ verdicts, uint32_t n)
-{
-	const uint64_t vd = (uint64_t)(uintptr_t)verdicts;
-	const uint32_t lead = min((uint32_t)(-vd & 3), n);
-	const uint32_t groups = (n - lead) / 4;
-	const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-	const uint32_t step = gridDim.x * blockDim.x;
-	for (uint32_t g = tid; g < groups; g += step) {
-		const uint32_t i = lead + 4 * g;
-		const u32x4 p = __builtin_nontemporal_load(reinterpret_cast<fr_gidx4 *>(
-			(uint64_t)(uintptr_t)pkt_of + 4ull * i));
-		*reinterpret_cast<uint32_t *>(verdicts + i) =
-			sf_verdict(pv, p.x) | sf_verdict(pv, p.y) << 8 | sf_verdict(pv, p.z) << 16 |
-			sf_verdict(pv, p.w) << 24;
-	}
-	// the bytes before the first 4-byte boundary and past the last whole group
-	const uint32_t rest = lead + 4 * groups;
-	if (tid < lead)
-		verdicts[tid] = (uint8_t)sf_verdict(pv, pkt_of[tid]);
-	if (tid < n - rest)
-		verdicts[rest + tid] = (uint8_t)sf_verdict(pv, pkt_of[rest + tid]);
 }
 
 __global__ __launch_bounds__(SC_LANES) void xfg_socks_frags_egress_kernel(
@@ -386,15 +355,11 @@ extern "C" int xfg_launch_socks_frags_heads(const struct xfg_socks_frags_kargs *
 					    void *stream)
 {
 	hipStream_t s = static_cast<hipStream_t>(stream);
-	const uint64_t want = ((uint64_t)a->n + 255) / 256;
 	// (the done pass's array lies in the state words: zeroed ahead of it)
 	if (hipMemsetAsync(a->state, 0, XFG_SOCKS_FRAGS_STATE_WORDS(a->n, a->nsocks) * 8, s) !=
 	    hipSuccess)
 		return -5;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_socks_frags_done_kernel, dim3(grid > want ? (unsigned)want : grid),
-			   dim3(256), 0, s, *a);
-	if (hipGetLastError() != hipSuccess)
+	if (xfg_flat_launch(xfg_socks_frags_done_kernel, ((uint64_t)a->n + 255) / 256, grid, stream, *a))
 		return -5;
 	return xfg_scan_launch(xfg_socks_frags_heads_kernel, a->state, 0, XFG_SOCKS_TILES(a->n), grid, s,
 			       *a);
@@ -403,14 +368,8 @@ extern "C" int xfg_launch_socks_frags_heads(const struct xfg_socks_frags_kargs *
 extern "C" int xfg_launch_socks_frags_spread(const uint8_t *pv, const uint32_t *pkt_of,
 					     uint8_t *verdicts, uint32_t n, unsigned grid, void *stream)
 {
-	hipStream_t s = static_cast<hipStream_t>(stream);
-	const uint64_t want = ((uint64_t)n / 4 + 255) / 256 + 1;
-	if (grid > want)
-		grid = (unsigned)want;
-	(void)hipGetLastError();
-	hipLaunchKernelGGL(xfg_socks_frags_spread_kernel, dim3(grid), dim3(256), 0, s, pv, pkt_of,
-			   verdicts, n);
-	return hipGetLastError() == hipSuccess ? 0 : -5;
+	return xfg_flat_launch(xfg_frags_spread_kernel<true>, ((uint64_t)n / 4 + 255) / 256 + 1, grid,
+			       stream, pv, pkt_of, verdicts, n);
 }
 
 extern "C" int xfg_launch_socks_frags_egress(const struct xfg_socks_frags_egress_kargs *a,
