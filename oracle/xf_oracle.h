@@ -2,11 +2,11 @@
  *
  * TEST INFRASTRUCTURE ONLY.  Only tests/, __graft_entry__.smoke() and
  * bench.py's cpu_baseline leg may load this; the product (libxdpfilter_gpu)
- * never links or calls it.  The reference itself cannot be built here
- * (xdpfilt_prog.h needs libbpf and the kernel's BPF map runtime; DESIGN.md
- * §2): parity of this restatement is pinned by the known-answer rows of
- * tests/kat.py, each restating a check of the reference's own tests
- * (under xdp-filter/tests/) with its file:line, and by tests/test_oracle.py.
+ * never links or calls it.  Parity of this restatement is pinned by the
+ * reference's own programs compiled for the host (oracle/ref/, DESIGN.md §2;
+ * tests/test_reference.py), by the known-answer rows of tests/kat.py, each
+ * restating a check of the reference's own tests (under xdp-filter/tests/)
+ * with its file:line, and by tests/test_oracle.py.
  */
 #ifndef XF_ORACLE_H
 #define XF_ORACLE_H

@@ -3,6 +3,8 @@
 ctypes bindings for:
   * tools/libxfsynth.so        seeded synthetic traffic (workloads C2..C5, fuzz)
   * oracle/build/liboracle.so  our CPU restatement of the xdpfilt_* program
+  * oracle/_ref/libref_*.so    the reference's own xdpfilt_*.c, compiled for the
+                               host (oracle/ref/; tests only)
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use the
 oracle binding, and only as the checker / the CPU baseline.
@@ -278,3 +280,51 @@ def run_oracle(features, data, lens, rules: RuleSet, stride=0, offsets=None,
     return verdicts, r, st.reshape(5, 2)
 
 
+# ----------------------------------------------------------------- reference
+REF_DIR = os.path.join(ROOT, "oracle", "_ref")
+_ref_libs: dict = {}
+
+
+def _ref_path(variant):
+    return os.path.join(REF_DIR, "libref_" + variant.removeprefix("xdpfilt_") + ".so")
+
+
+def have_reference() -> bool:
+    """True when all ten host builds of the reference's programs are present."""
+    return all(os.path.exists(_ref_path(v)) for v, _ in VARIANTS)
+
+
+def reference(variant):
+    """The host build of the reference's xdpfilt_<variant>.c (oracle/ref/)."""
+    lib = _ref_libs.get(variant)
+    if lib is None:
+        lib = C.CDLL(_ref_path(variant))
+        lib.ref_features.restype = C.c_uint32
+        lib.ref_features.argtypes = []
+        lib.ref_run.argtypes = [_u8p, _u64p, C.c_uint32, _u32p, C.c_uint64, _u64p,
+                                _u8p, _u64p, C.c_uint32, _u8p, _u64p, C.c_uint32,
+                                _u8p, _u64p, C.c_uint32, _u8p, _u64p]
+        _ref_libs[variant] = lib
+    return lib
+
+
+def run_reference(variant, data, lens, rules: RuleSet, stride=0, offsets=None, stats=None):
+    """Run the reference's own program `variant` ("xdpfilt_dny_all", ...);
+    returns (verdicts, rules_after, stats[5,2]) as run_oracle does."""
+    lib = reference(variant)
+    r = rules.prepared().copy()
+    n = len(lens)
+    verdicts = np.zeros(n, np.uint8)
+    st = np.zeros(10, np.uint64) if stats is None else stats.reshape(10)
+    data = np.ascontiguousarray(data, np.uint8)
+    lens = np.ascontiguousarray(lens, np.uint32)
+    offs = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
+    rc = lib.ref_run(ptr(data), ptr(offs, _u64p), stride, ptr(lens, _u32p), n,
+                     ptr(r.ports, _u64p),
+                     ptr(r.v4_keys), ptr(r.v4_vals, _u64p), len(r.v4_vals),
+                     ptr(r.v6_keys), ptr(r.v6_vals, _u64p), len(r.v6_vals),
+                     ptr(r.eth_keys), ptr(r.eth_vals, _u64p), len(r.eth_vals),
+                     ptr(verdicts), ptr(st, _u64p))
+    if rc:
+        raise RuntimeError("reference run failed (no arena below 4 GiB?)")
+    return verdicts, r, st.reshape(5, 2)
