@@ -284,8 +284,9 @@ int xfg_classify_descs(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch
  *
  * Capture by whole packet: xfg_capture_descs_frags with count = counts[1]
  * (xfg_capture_descs keeps capturing record by record, each record's bytes
- * under its packet's verdict).  Not covered: xfg_classify_xsk_host, and the
- * CLI.
+ * under its packet's verdict).  A second context on the packets this one
+ * passed on: xfg_classify_descs_frags_chain with count = counts[1].  Not
+ * covered: xfg_classify_xsk_host, and the CLI.
  */
 #define XFG_XDP_PKT_CONTD (1u << 0)          /* headers/linux/if_xdp.h:123 */
 
@@ -356,9 +357,10 @@ int xfg_classify_descs_frags(xfg_ctx *ctx, int dev, const struct xfg_desc_batch 
  *
  * Many sockets need nothing of their own: with xfg_socks.flat given,
  * xfg_classify_socks leaves a plain descriptor array, and
- * xfg_classify_descs_chain takes it.  Not covered: multi-buffer batches (a
- * chained stage would have to select head records only and spread again), the
- * host-memory path, and the CLI.
+ * xfg_classify_descs_chain takes it.  Multi-buffer batches (XDP_USE_SG
+ * sockets) take xfg_classify_descs_frags_chain below: xfg_classify_descs_chain
+ * would run the program on continuation records, which are not packets.  Not
+ * covered: the host-memory path, and the CLI.
  */
 #define XFG_CHAIN_PASS (1u << XFG_XDP_PASS)   /* xdp-filter's own chain_call_actions */
 
@@ -375,6 +377,80 @@ int xfg_classify_chain(xfg_ctx *ctx, int dev, const struct xfg_batch *batch,
 		       struct xfg_chain *ch, uint8_t *verdicts, void *stream);
 int xfg_classify_descs_chain(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
 			     struct xfg_chain *ch, uint8_t *verdicts, void *stream);
+
+/*
+ * A chained stage over a multi-buffer batch: run this context's program only
+ * on the packets an earlier multi-buffer stage passed on, by their head
+ * records, and give every record of such a packet the new verdict.
+ *
+ * @verdicts (device, count bytes) is input and output: what
+ * xfg_classify_descs_frags or xfg_classify_socks_frags -- on another context,
+ * or this one -- wrote for the same records.  Packets are formed exactly as
+ * xfg_capture_descs_frags forms them (live / eop / head, stated there), so the
+ * call serves both: after xfg_classify_descs_frags pass count = counts[1];
+ * after xfg_classify_socks_frags pass sk->flat as a plain array (mask
+ * 0xffffffff) of count = total records, whose XFG_VERDICT_NONE bytes keep the
+ * sockets apart.  The packet of head h is records h..e; it exists only if every
+ * one of them is live and e < count.  A complete packet is selected by its
+ * head's byte alone: v[h] < 32 and bit v[h] of chain_mask set.  A live run that
+ * ends -- at a record that is not live, or at the end of the batch -- without
+ * an end-of-packet record is no packet and is never selected.
+ *
+ * The verdicts, rule hit counts and per-action statistics of THIS context are
+ * exactly those of xfg_classify_descs over the plain array of the selected
+ * packets' head records, in their order, each with its head record's len;
+ * xfg_last_path and xfg_open_opts.descs_min_packets behave as for such a call
+ * of counts[0] records.  The earlier stage's context is not touched.  Every
+ * record h..e of a selected packet gets the new verdict byte; every other byte
+ * of @verdicts stays as it was, XFG_VERDICT_NONE bytes and the bytes around an
+ * unaligned @verdicts included.  So xfg_ring_egress (XFG_EGRESS_MULTIBUF),
+ * xfg_socks_frags_egress and xfg_capture_descs_frags take the result as they
+ * take the earlier stage's.  If every record is an end-of-packet record and no
+ * byte is XFG_VERDICT_NONE, then idx, counts[0] and the verdict bytes are
+ * those of xfg_classify_descs_chain.
+ *
+ * Out: counts[0] = packets selected, counts[1] = records in them, counts[2] =
+ * all other records (count - counts[1]); HOST memory, valid when the call
+ * returns.  idx (device, count x u32, or NULL): the selected packets' head
+ * record indices, ascending, counts[0] of them.
+ *
+ * Three steps on the device, as for xfg_classify_descs_chain: the pre-pass
+ * (two kernels whatever the packets' shapes: a scan over the records that
+ * numbers the runs between packet boundaries, then a scan over those runs that
+ * ranks the selected complete ones and gathers their head records into a plain
+ * descriptor array in library scratch); the two counts read back to the host;
+ * the counts[0] heads classified, and their verdicts spread over the records
+ * (one kernel).  No record walks its packet: a packet of thousands of records
+ * costs what that many single records cost.  16 bytes a record of library
+ * scratch beside the frags calls', grown on demand.  The read-back is the
+ * call's one host synchronisation, after it has ordered itself behind @stream,
+ * deliberate for the reason given at xfg_classify_descs_frags.  The classify
+ * and the spread are stream-ordered; the call returns without waiting for
+ * them, and @stream's later work runs after them.
+ *
+ * -EINVAL: what xfg_classify_descs_chain refuses, of this structure: ch ==
+ * NULL, sz below the structure's size, a non-zero flags, idx not 4-byte
+ * aligned, verdicts == NULL with count != 0, count >= 2^32, and what
+ * xfg_classify_descs refuses of the batch.  count == 0: counts {0, 0, 0},
+ * nothing launched, whatever the context's devices.  -ENODEV on a host-only
+ * context, after these checks; no device pointer is touched before it.
+ * chain_mask == 0 or no packet selected: counts {0, 0, count}, nothing
+ * classified, no statistic changes, verdicts untouched.  -EIO if a count read
+ * back is impossible.  Not covered: the host-memory ring
+ * (xfg_classify_xsk_host), and the CLI.
+ */
+struct xfg_frags_chain {
+	size_t sz;            /* sizeof(struct xfg_frags_chain), for extension */
+	uint32_t chain_mask;  /* bit v: a packet whose HEAD's verdict byte is v (< 32) runs this context's program */
+	uint32_t flags;       /* 0; any bit set: -EINVAL */
+	uint32_t *idx;        /* device, count x u32, 4-byte aligned, or NULL (library scratch):
+	                       * out, the selected packets' head record indices, ascending */
+	uint64_t counts[3];   /* HOST, out: packets selected, records in them,
+	                       * all other records (count - counts[1]) */
+};
+
+int xfg_classify_descs_frags_chain(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
+				   struct xfg_frags_chain *ch, uint8_t *verdicts, void *stream);
 
 /*
  * Host-resident batch (struct xfg_batch in host memory): classifies it on
@@ -724,7 +800,9 @@ int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
  * Capture by whole packet: xfg_capture_descs_frags over sk->flat with the
  * call's verdicts; the XFG_VERDICT_NONE bytes keep a socket's trailing records
  * and the next socket's head apart (xfg_capture_descs captures record by
- * record, and skips the XFG_VERDICT_NONE records).  Not covered: the
+ * record, and skips the XFG_VERDICT_NONE records).  A second context on the
+ * packets this one passed on: xfg_classify_descs_frags_chain over sk->flat the
+ * same way, before xfg_socks_frags_egress.  Not covered: the
  * host-memory ring (xfg_classify_xsk_host), the CLI, sockets over different
  * UMEMs.
  */
@@ -898,6 +976,11 @@ int xfg_classify_descs_frags_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_
  * the scatter (0 for a step that did not run). */
 int xfg_classify_descs_chain_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
 				   struct xfg_chain *ch, uint8_t *verdicts, double ms[3]);
+/* One xfg_classify_descs_frags_chain call on the library's stream, timed the
+ * same way: ms[0] the pre-pass (both kernels), ms[1] the classify of the
+ * selected packets' heads, ms[2] the spread (0 for a step that did not run). */
+int xfg_classify_descs_frags_chain_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *batch,
+					 struct xfg_frags_chain *ch, uint8_t *verdicts, double ms[3]);
 
 /* Streaming-read probe: average duration of a kernel that reads @bytes of
  * device memory at @src with 16-byte non-temporal loads (the achievable HBM

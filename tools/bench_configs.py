@@ -53,6 +53,14 @@
       verdicts (the same payload bytes, three times the blocks) -- timed as
       c3c's legs are, with the bytes moved and their share of the
       streaming-read rate
+  c3mch c3m's batch, classified by xfg_classify_descs_frags, as the first stage
+      of a chain (xfg_classify_descs_frags_chain): half the packets' verdict
+      bytes pre-set to PASS, once every other packet and once a contiguous
+      half.  The call by wall clock (to its return and to the stream's end) and
+      its three steps (xfg_classify_descs_frags_chain_timed); beside them the
+      three steps of xfg_classify_descs_frags over a pre-built ring of the
+      selected packets alone (the floor), with the bytes the pre-pass and the
+      spread move
   c3s  C3's rules and frames in c3d's UMEM, scattered over --socks sockets of
       --batch records (64 x 64 by default; --sweep: 4, 64, 1024 sockets x 64,
       256 records): a poll round as xfg_classify_descs + xfg_ring_egress a
@@ -642,6 +650,83 @@ def run_c3mc(args):
     print(json.dumps(line), flush=True)
 
 
+def run_c3mch(args):
+    """c3m's batch as the second stage of a chain over multi-buffer packets,
+    half the packets selected."""
+    import numpy as np
+    cm = c3m_workload(args, "c3mch")
+    w, nrec, entries, first, runs = cm.w, cm.nrec, cm.entries, cm.first, cm.runs
+    f, n = w.f, w.n
+    ring = dict(first=first, mask=entries - 1)
+    descs = cm.d_descs.download(np.zeros((entries, 2), np.uint64))
+    recs = descs[(first + np.arange(nrec)) & (entries - 1)].reshape(n, 3, 2)
+    del descs
+    nsel = n // 2
+    d_half, d_hv = f.alloc(16 * 3 * nsel), f.alloc(3 * nsel)
+    line = {"config": "c3mch", "program": f.prog_name, "packets": n, "records": nrec,
+            "selected_packets": nsel, "ring_entries": entries, "iters": args.iters, "runs": runs,
+            "setup_s": round(w.setup_s + time.time() - cm.t0, 1)}
+    for name in ("alternating", "contiguous"):
+        pre = np.ones((n, 3), np.uint8)            # DROP: not selected by XFG_CHAIN_PASS
+        if name == "alternating":
+            pre[0::2] = 2
+        else:
+            pre[n // 4:n // 4 + nsel] = 2
+        sel = np.flatnonzero(pre[:, 0] == 2)
+        assert len(sel) == nsel
+        # the floor: the selected packets alone, as a ring of their own
+        d_half.upload(np.ascontiguousarray(recs[sel]))
+        fl = (w.d_umem.ptr, d_half.ptr, 3 * nsel, d_hv.ptr)
+        floor = []
+        for k in range(runs + 1):
+            counts, ms = f.classify_descs_frags_timed(*fl)
+            assert counts == (nsel, 3 * nsel, 0), counts
+            if k:
+                floor.append([round(m, 4) for m in ms])
+        floor_path = f.last_path()
+        steps, ret_ms, end_ms = [], [], []
+        for k in range(runs + 1):                  # (the first call grows the scratch: not counted)
+            cm.d_verd.upload(pre)
+            f.sync()
+            counts, ms = f.classify_descs_frags_chain_timed(w.d_umem.ptr, cm.d_descs.ptr, nrec,
+                                                            cm.d_verd.ptr, **ring)
+            assert counts == (nsel, 3 * nsel, nrec - 3 * nsel), counts
+            got = cm.d_verd.download(np.zeros(nrec, np.uint8)).reshape(n, 3)
+            want = pre.copy()
+            want[sel] = cm.hv[sel, None]
+            assert np.array_equal(got, want), "verdicts differ from c3d's of the selected heads"
+            cm.d_verd.upload(pre)
+            f.sync()
+            t0 = time.perf_counter()
+            f.classify_descs_frags_chain(w.d_umem.ptr, cm.d_descs.ptr, nrec, cm.d_verd.ptr, **ring)
+            t1 = time.perf_counter()
+            f.sync()
+            t2 = time.perf_counter()
+            if k:
+                steps.append([round(m, 4) for m in ms])
+                ret_ms.append(round((t1 - t0) * 1e3, 4))
+                end_ms.append(round((t2 - t0) * 1e3, 4))
+        best = [min(s[j] for s in steps) for j in range(3)]
+        fbest = [min(s[j] for s in floor) for j in range(3)]
+        # bytes the two pre-pass kernels move: a verdict byte and the options a
+        # record, seg_of out, the fill and the read-back of head_of_seg and
+        # end_of_seg, rank_of_seg out; a head's index and its end a packet; a
+        # verdict byte, the head record in and out and idx a selected packet
+        pre_bytes = nrec * (1 + 4 + 4 + 8 + 8 + 4) + 8 * n + nsel * (1 + 16 + 16 + 4)
+        spread_bytes = nrec * (4 + 4) + 3 * nsel * 2 + nsel
+        line[name] = {
+            "frags_chain_steps_ms": steps, "frags_chain_path": f.last_path(),
+            "frags_chain_wall_to_return_ms": ret_ms, "frags_chain_wall_to_stream_end_ms": end_ms,
+            "classify_descs_frags_selected_alone_steps_ms": floor, "floor_path": floor_path,
+            "overhead_over_floor_ms": round(sum(best) - sum(fbest), 4),
+            "prepass_plus_spread_ms": round(best[0] + best[2], 4),
+            "prepass_bytes": pre_bytes, "spread_bytes": spread_bytes,
+            "prepass_GBps": round(pre_bytes / (best[0] * 1e-3) / 1e9, 1),
+            "spread_GBps": round(spread_bytes / (best[2] * 1e-3) / 1e9, 1)}
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
 def run_c3m(args):
     """c3d's frames as the heads of 3-record packets (see the module text)."""
     import numpy as np
@@ -1022,6 +1107,8 @@ def run(name, args):
         return run_c3m(args)
     if name == "c3mc":
         return run_c3mc(args)
+    if name == "c3mch":
+        return run_c3mch(args)
     kind = {"c2": 2, "c3": 3, "c4": 4, "c5": 5, "c3sd": 3, "c3e": 3}[name]
     n = 1 << (args.log2_packets or {"c2": 24, "c3": 24, "c4": 23, "c5": 23, "c3sd": 24, "c3e": 24}[name])
     stride = 64 if kind in (2, 3) else 1536

@@ -50,6 +50,9 @@ int xfg_launch_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *
 int xfg_launch_chain_select(const struct xfg_chain_kargs *a, unsigned grid, void *stream);
 int xfg_launch_chain_scatter(const uint8_t *pv, const uint32_t *idx, uint8_t *verdicts,
 			     uint32_t cnt, unsigned grid, void *stream);
+int xfg_launch_frags_chain_select(const struct xfg_frags_chain_kargs *a, unsigned grid, void *stream);
+int xfg_launch_frags_chain_spread(const uint8_t *pv, const uint32_t *seg, uint8_t *verdicts,
+				  uint32_t n, unsigned grid, void *stream);
 int xfg_launch_socks_gather(const struct xfg_socks_gather_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_egress(const struct xfg_socks_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_frags_heads(const struct xfg_socks_frags_kargs *a, unsigned grid, void *stream);
@@ -174,6 +177,12 @@ struct xfg_dev {
 	uint8_t *fr_pv;
 	uint32_t *fr_pkt;
 	uint64_t fr_heads_bytes, fr_pv_bytes, fr_pkt_bytes;
+	/* a chained stage over a multi-buffer batch
+	 * (xfg_classify_descs_frags_chain, under frags_lock): the records'
+	 * segments and the segments' ranks, heads and ends (xfg_layout.h); made
+	 * by its pre-pass */
+	uint32_t *fc_seg;
+	uint64_t fc_seg_bytes;
 	/* capture of multi-buffer packets (xfg_capture_descs_frags): a record's
 	 * bytes of its packet before it, a head's {bytes, records} */
 	uint32_t *cf_off;
@@ -509,6 +518,7 @@ static void dev_free(struct xfg_dev *d)
 	hipFree(d->fr_heads);
 	hipFree(d->fr_pv);
 	hipFree(d->fr_pkt);
+	hipFree(d->fc_seg);
 	hipFree(d->cf_off);
 	hipFree(d->cf_tot);
 	for (int k = 0; k < SOCKS_SLOTS; k++) {
@@ -2086,7 +2096,8 @@ struct staged {
 	pthread_mutex_t *lock;  /* the call's outer lock: frags_lock, socks_lock */
 	uint64_t words;         /* status words of d->cstatus the pre-pass uses */
 	uint64_t n;             /* records fr_heads and fr_pv are sized for (0: neither) */
-	uint32_t *idx;          /* their indices: the caller's, or NULL: fr_pkt, sized too */
+	uint32_t *idx;          /* their indices: the caller's, or NULL: fr_pkt, sized too
+	                         * (@got may point it at what the post-pass reads instead) */
 	uint8_t *verdicts;      /* the caller's verdict bytes */
 	const void *umem;       /* classify(): the frames' base, */
 	const void *descs;      /* their descriptors (NULL: fr_heads; @pre may set it) */
@@ -2426,6 +2437,95 @@ int xfg_classify_descs_chain_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_
 				   struct xfg_chain *ch, uint8_t *verdicts, double ms[3])
 {
 	return db && ms ? chain_run(ctx, dev, NULL, db, ch, verdicts, NULL, ms) : -EINVAL;
+}
+
+/* A chained stage over a multi-buffer batch (include/xdpfilter_gpu.h), a
+ * staged call under frags_lock: the record pass and the segment pass over the
+ * records and the earlier stage's verdict bytes, the selected packets and
+ * their records read back (the classify launch is planned from the packets),
+ * the packets' head records classified as a plain descriptor array, and their
+ * verdicts spread over all records by segment, if any packet was selected.
+ * Its scratch is the frags calls' (the heads' room, the per-packet verdicts,
+ * the packet indices' for idx) and the segment arrays, grown by the pre-pass
+ * with the stream entered as the capture scan's are.  The argument checks come
+ * first and the empty batch next, neither needing a device. */
+static int frags_chain_pre(struct xfg_dev *d, struct staged *j)
+{
+	struct xfg_frags_chain_kargs a = *(const struct xfg_frags_chain_kargs *)j->arg;
+	const int err = scratch(d, (void **)&d->fc_seg, &d->fc_seg_bytes, XFG_FRAGS_CHAIN_SEG_BYTES(j->n));
+	if (err)
+		return err;
+	a.idx = j->idx;
+	a.sel = d->fr_heads;
+	a.seg = d->fc_seg;
+	a.state = d->cstatus;
+	/* (four workgroups a CU: all of them resident) */
+	return xfg_launch_frags_chain_select(&a, (unsigned)d->ncu * 4, d->stream);
+}
+
+static int frags_chain_got(struct xfg_dev *d, struct staged *j)
+{
+	struct xfg_frags_chain *ch = j->out;
+	unsigned long long got[2] = { 0, 0 };
+	const int err = dev_read(d, got, d->cstatus + 2, sizeof(got));
+	if (err)
+		return err;
+	/* (a packet has at least one record) */
+	if (got[1] > j->n || got[0] > got[1] || (got[0] != 0) != (got[1] != 0))
+		return -EIO;
+	ch->counts[0] = j->count = got[0];
+	ch->counts[1] = got[1];
+	ch->counts[2] = j->n - got[1];
+	/* the spread goes over all records, by their segments */
+	j->back = got[0] ? j->n : 0;
+	j->idx = d->fc_seg;
+	return 0;
+}
+
+static int frags_chain_run(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+			   struct xfg_frags_chain *ch, uint8_t *verdicts, void *stream, double *ms)
+{
+	if (!ctx || !db || !ch || ch->sz < sizeof(*ch) || ch->flags || ((uintptr_t)ch->idx & 3))
+		return -EINVAL;
+	const uint64_t n = db->count;
+	if (n > 0xffffffffull || (n && !verdicts) || (n && descs_bad(db)))
+		return -EINVAL;
+	if (ms)
+		ms[0] = ms[1] = ms[2] = 0;
+	if (!n) {
+		ch->counts[0] = ch->counts[1] = ch->counts[2] = 0;
+		return 0;
+	}
+	int err = dev_check(ctx, dev);
+	if (err)
+		return err;
+	ch->counts[0] = ch->counts[1] = 0;
+	ch->counts[2] = n;
+	if (!ch->chain_mask)
+		return 0;
+	const struct xfg_frags_chain_kargs a = {
+		.descs = db->descs, .verdicts = verdicts, .n = (uint32_t)n, .first = db->first,
+		.mask = db->mask, .chain_mask = ch->chain_mask,
+	};
+	struct staged j = {
+		.lock = &ctx->dev[dev].frags_lock, .words = XFG_FRAGS_CHAIN_STATE_WORDS(n), .n = n,
+		.idx = ch->idx, .verdicts = verdicts, .umem = db->umem,
+		.pre = frags_chain_pre, .got = frags_chain_got, .post = xfg_launch_frags_chain_spread,
+		.arg = &a, .out = ch,
+	};
+	return staged_run(ctx, dev, &j, stream, ms);
+}
+
+int xfg_classify_descs_frags_chain(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+				   struct xfg_frags_chain *ch, uint8_t *verdicts, void *stream)
+{
+	return frags_chain_run(ctx, dev, db, ch, verdicts, stream, NULL);
+}
+
+int xfg_classify_descs_frags_chain_timed(xfg_ctx *ctx, int dev, const struct xfg_desc_batch *db,
+					 struct xfg_frags_chain *ch, uint8_t *verdicts, double ms[3])
+{
+	return ms ? frags_chain_run(ctx, dev, db, ch, verdicts, NULL, ms) : -EINVAL;
 }
 
 /* Many sockets over one UMEM (include/xdpfilter_gpu.h): what both calls check

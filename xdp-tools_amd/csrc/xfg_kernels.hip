@@ -2209,6 +2209,10 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // scheme with the chain mask as the predicate
 #include "xfg_chain.hip"
 
+// a chained stage over a multi-buffer batch (segments, then the selected
+// packets' heads; verdict spread): two plain sum scans of the same scheme
+#include "xfg_frags_chain.hip"
+
 // many sockets over one UMEM (gather, segmented egress): the egress kernel's
 // scheme with a socket table in the place of one ring
 #include "xfg_socks.hip"

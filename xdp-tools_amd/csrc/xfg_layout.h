@@ -421,6 +421,41 @@ struct xfg_chain_kargs {
 #define XFG_CHAIN_TILES(n) (((uint64_t)(n) + XFG_CHAIN_TILE - 1) / XFG_CHAIN_TILE)
 #define XFG_CHAIN_STATE_WORDS(n) ((XFG_CHAIN_TILES(n) + 5) & ~1ull)
 
+/* Arguments of the two pre-pass kernels of a chained stage over a multi-buffer
+ * batch (xfg_frags_chain.hip, xfg_classify_descs_frags_chain()): the records,
+ * the earlier stage's verdict bytes, the selection; out, the k-th selected
+ * packet's head record index idx[k] and that record sel[k] (room for n each);
+ * and seg, 4 * n u32 of library scratch in four arrays of n
+ * (XFG_FRAGS_CHAIN_*_AT): record i's segment seg_of[i]; a segment's place in
+ * the selection rank_of_seg[s] (ones: none), which the spread finds behind
+ * seg_of through that one pointer; its head record head_of_seg[s] and its
+ * end-of-packet record end_of_seg[s], both filled with ones by the launch.
+ * The state words are two sets laid out as the head pass's, the record pass's
+ * and then the segment pass's -- word 0 the tile ticket, from word 4 one status
+ * word a tile -- with the selected packets in word 2 of the first set and the
+ * records in them in word 3; zeroed by the launch function. */
+struct xfg_frags_chain_kargs {
+	const void *descs;              /* struct xdp_desc records */
+	const uint8_t *verdicts;
+	uint32_t *idx;
+	void *sel;
+	uint32_t *seg;
+	unsigned long long *state;
+	uint32_t n;                     /* records, >= 1 */
+	uint32_t first, mask;
+	uint32_t chain_mask;            /* != 0 */
+};
+#define XFG_FRAGS_CHAIN_TILE 2048u   /* records, or segments, a tile: 256 lanes x 8 passes */
+#define XFG_FRAGS_CHAIN_TILES(n) (((uint64_t)(n) + XFG_FRAGS_CHAIN_TILE - 1) / XFG_FRAGS_CHAIN_TILE)
+#define XFG_FRAGS_CHAIN_SET_WORDS(n) ((XFG_FRAGS_CHAIN_TILES(n) + 5) & ~1ull)
+#define XFG_FRAGS_CHAIN_STATE_WORDS(n) (2 * XFG_FRAGS_CHAIN_SET_WORDS(n))
+#define XFG_FRAGS_CHAIN_SEG_OF_AT(n) 0ull
+#define XFG_FRAGS_CHAIN_RANK_AT(n) ((uint64_t)(n))
+#define XFG_FRAGS_CHAIN_HEAD_AT(n) (2 * (uint64_t)(n))
+#define XFG_FRAGS_CHAIN_END_AT(n) (3 * (uint64_t)(n))
+#define XFG_FRAGS_CHAIN_SEG_BYTES(n) (16 * (uint64_t)(n))
+#define XFG_FRAGS_CHAIN_NONE 0xffffffffu   /* no rank, no head, no end */
+
 /* Many sockets over one UMEM (xfg_socks.hip, xfg_classify_socks() and
  * xfg_socks_egress()).  A socket's three rings as the kernels read them, one
  * 16-byte load each; a launch's table in device memory is nsocks of these and,

@@ -66,6 +66,7 @@ EXPORTS = [
     "xfg_classify_descs_frags_timed", "xfg_classify_socks", "xfg_socks_egress",
     "xfg_classify_socks_frags", "xfg_socks_frags_egress", "xfg_capture_descs_frags",
     "xfg_classify_chain", "xfg_classify_descs_chain", "xfg_classify_descs_chain_timed",
+    "xfg_classify_descs_frags_chain", "xfg_classify_descs_frags_chain_timed",
 ]
 CAPTURE_HEAD_ONLY = 1        # XFG_CAPTURE_HEAD_ONLY
 SOCKS_MAX = 1024
@@ -126,6 +127,12 @@ class Chain(C.Structure):
     """struct xfg_chain (xfg_classify_chain, xfg_classify_descs_chain)."""
     _fields_ = [("sz", C.c_size_t), ("chain_mask", C.c_uint32), ("flags", C.c_uint32),
                 ("idx", C.c_void_p), ("counts", C.c_uint64 * 2)]
+
+
+class FragsChain(C.Structure):
+    """struct xfg_frags_chain (xfg_classify_descs_frags_chain)."""
+    _fields_ = [("sz", C.c_size_t), ("chain_mask", C.c_uint32), ("flags", C.c_uint32),
+                ("idx", C.c_void_p), ("counts", C.c_uint64 * 3)]
 
 
 class Sock(C.Structure):
@@ -237,6 +244,11 @@ def _load():
         "xfg_classify_descs_chain_timed": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch),
                                                      C.POINTER(Chain), vp,
                                                      C.POINTER(C.c_double)]),
+        "xfg_classify_descs_frags_chain": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch),
+                                                     C.POINTER(FragsChain), vp, vp]),
+        "xfg_classify_descs_frags_chain_timed": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch),
+                                                           C.POINTER(FragsChain), vp,
+                                                           C.POINTER(C.c_double)]),
         "xfg_classify_xsk_host": (C.c_int, [vp, C.c_int, C.POINTER(DescBatch), C.c_uint64, vp]),
         "xfg_host_register": (C.c_int, [vp, vp, C.c_size_t]),
         "xfg_host_unregister": (C.c_int, [vp, vp]),
@@ -642,6 +654,34 @@ class Filter:
         ms = (C.c_double * 3)()
         _check(lib.xfg_classify_descs_chain_timed(self.ctx, dev, C.byref(b), C.byref(ch),
                                                   verdicts_ptr, ms), "classify_descs_chain_timed")
+        return tuple(int(c) for c in ch.counts), tuple(ms)
+
+    def classify_descs_frags_chain(self, umem_ptr, descs_ptr, count, verdicts_ptr,
+                                   chain_mask=CHAIN_PASS, idx_ptr=None, first=0,
+                                   mask=0xffffffff, dev=0, stream=None):
+        """A chained stage over a multi-buffer batch
+        (xfg_classify_descs_frags_chain): this context's program on the
+        complete packets whose head's byte at verdicts_ptr is in chain_mask,
+        the new verdict on all their records.  Returns the counts (packets
+        selected, records in them, all other records)."""
+        b = DescBatch(umem_ptr, descs_ptr, first, mask, count)
+        ch = FragsChain(C.sizeof(FragsChain), chain_mask, 0, idx_ptr)
+        _check(lib.xfg_classify_descs_frags_chain(self.ctx, dev, C.byref(b), C.byref(ch),
+                                                  verdicts_ptr, stream),
+               "classify_descs_frags_chain")
+        return tuple(int(c) for c in ch.counts)
+
+    def classify_descs_frags_chain_timed(self, umem_ptr, descs_ptr, count, verdicts_ptr,
+                                         chain_mask=CHAIN_PASS, idx_ptr=None, first=0,
+                                         mask=0xffffffff, dev=0):
+        """One such call with its steps timed: (counts, (pre-pass ms, classify
+        ms, spread ms)) (xfg_classify_descs_frags_chain_timed)."""
+        b = DescBatch(umem_ptr, descs_ptr, first, mask, count)
+        ch = FragsChain(C.sizeof(FragsChain), chain_mask, 0, idx_ptr)
+        ms = (C.c_double * 3)()
+        _check(lib.xfg_classify_descs_frags_chain_timed(self.ctx, dev, C.byref(b), C.byref(ch),
+                                                        verdicts_ptr, ms),
+               "classify_descs_frags_chain_timed")
         return tuple(int(c) for c in ch.counts), tuple(ms)
 
     def host_register(self, arr: np.ndarray):
