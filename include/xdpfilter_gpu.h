@@ -600,6 +600,123 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e,
 		    const uint8_t *verdicts, void *stream);
 
 /*
+ * Steered egress: the passed frames of a classified RX batch spread over the
+ * TX rings of K workers by flow, on the device -- "drop the attack, spread the
+ * rest".  Worker q owns TX ring q; a flow always takes the same ring, in
+ * arrival order.  This is xdp-bench redirect-cpu's cpumap_l4_hash,
+ * cpumap_l4_sport and cpumap_l4_dport (xdp-bench/xdp_redirect_cpumap.bpf.c:
+ * 506-653) with a TX ring in the place of a CPU.
+ *
+ * Record i is rx_descs[(rx_first + i) & rx_mask] with verdict byte
+ * verdicts[i], as for xfg_ring_egress.  A record whose verdict is
+ * XFG_XDP_PASS gets a queue, chosen from the frame's bytes [0, len) in the
+ * UMEM exactly as the program chooses from [data, data_end):
+ *
+ *   parse_eth (:53-96): a frame with len < 14, with an ethertype below 0x0600,
+ *   or whose first or second 802.1Q/802.1AD tag does not fit in the frame is
+ *   refused.  At most two tags are skipped; a third leaves a VLAN ethertype,
+ *   which is neither IPv4 nor IPv6.  A refused frame goes to queue skip_queue
+ *   (the program returns XDP_PASS for it, "just skip": here the caller's
+ *   slow-path worker) and is counted in counts[nqueues + 1].  With l3 the
+ *   offset behind the tags:
+ *
+ *   XFG_STEER_L4_HASH (:469-553): IPv4 -- l3 + 20 > len: hash 0; else
+ *   SuperFastHash (xdp-bench/hash_func01.h) of the four bytes of saddr + daddr
+ *   with initial value 15485863 + protocol, the addresses loaded as the
+ *   program loads them (little-endian 32-bit loads of network-order bytes,
+ *   wrapping sum; swapping source and destination gives the same hash).  IPv6
+ *   -- l3 + 40 > len: hash 0; else the same over the wrapping sum of the eight
+ *   address words, with 15485863 + nexthdr.  ARP and everything else: hash 0.
+ *   idx = hash % navail.
+ *
+ *   XFG_STEER_L4_SPORT / XFG_STEER_L4_DPORT (:98-213,567-641): the port, in
+ *   host order, read at the fixed offset l3 + 20 (IPv4) or l3 + 40 (IPv6) --
+ *   the program looks neither at ihl nor at extension headers (:111,134), so
+ *   neither does this.  It is 0 unless the protocol (IPv4) or nexthdr (IPv6)
+ *   is TCP and a 20-byte TCP header fits in the frame, or UDP and an 8-byte
+ *   UDP header fits.  idx = port % navail.
+ *
+ *   queue = avail[idx] (the program's cpus_available, navail its cpus_count:
+ *   a queue named twice gets twice the share).  avail == NULL: the identity,
+ *   navail = nqueues.
+ *
+ * The k-th record in batch order that takes queue q becomes
+ * queues[q].tx_descs[(tx_first + k) & tx_mask] of that queue: addr and len as
+ * received, options 0.  The j-th record with any other verdict hands its chunk
+ * back: fill_addrs[(fill_first + j) & fill_mask] = addr & ((1 << 48) - 1);
+ * fill_addrs == NULL: no fill entries are written.  counts (device, (nqueues +
+ * 2) x u64): counts[q] the TX records of queue q, counts[nqueues] the other
+ * records (whether their fill entries were written or not), counts[nqueues +
+ * 1] the refused frames (they are among counts[skip_queue] too).  Ring entries
+ * past those counts are not written.  queue_of[i] (device, count bytes), when
+ * given, is record i's queue, or XFG_QUEUE_NONE for a record that is not PASS.
+ *
+ * queues and avail are HOST memory and may be reused as soon as the call
+ * returns: they reach the device through the pinned staging slots of the
+ * socket calls, so the call makes no host synchronisation, and after
+ * xfg_classify_descs on the same stream it needs none.  A queue with tx_descs
+ * == NULL is refused if an avail entry or skip_queue names it.
+ *
+ * XFG_EGRESS_SWAP_MACS, masks, index wrap, ring overlap and stream ordering
+ * are as for xfg_ring_egress; every TX ring that can be written and the fill
+ * ring need at least count entries.  The UMEM is read for every PASS frame:
+ * the first 64 bytes that lie below len rounded up to 16 (frame starts are
+ * 16-byte aligned), and four bytes at 64 for a double-tagged IPv6 frame in
+ * XFG_STEER_L4_DPORT whose port counts.  count == 0: the counts are zeroed and
+ * nothing else is written.
+ *
+ * The call takes one RX ring or plain array.  For a poll round of many
+ * sockets it runs over the flat array xfg_classify_socks leaves, with mask
+ * 0xffffffff.
+ *
+ * -EINVAL: s == NULL, sz below the structure's size, nqueues 0 or above
+ * XFG_STEER_QUEUES_MAX, navail 0 or above XFG_STEER_AVAIL_MAX (avail given),
+ * an avail entry or skip_queue >= nqueues or naming a queue without a ring, an
+ * unknown mode, a flag other than XFG_EGRESS_SWAP_MACS (XFG_EGRESS_MULTIBUF
+ * too), umem, rx_descs, verdicts or counts NULL with count != 0 (counts NULL
+ * always), a pointer that is not 8-byte aligned, a mask that is not 2^k - 1, a
+ * written ring with fewer than count entries, count >= 2^32.  -ENODEV on a
+ * host-only context (after these checks; no device pointer is dereferenced
+ * before it).
+ *
+ * Not covered: multi-buffer packets (XFG_EGRESS_MULTIBUF is refused: a
+ * packet's records would have to follow its head's queue), the host-memory
+ * path (xfg_classify_xsk_host), the CLI, and the program's round-robin,
+ * l4-proto and l4-filter modes.
+ */
+#define XFG_STEER_QUEUES_MAX 64u
+#define XFG_STEER_AVAIL_MAX  256u
+#define XFG_STEER_L4_HASH  0u   /* cpumap_l4_hash  */
+#define XFG_STEER_L4_SPORT 1u   /* cpumap_l4_sport */
+#define XFG_STEER_L4_DPORT 2u   /* cpumap_l4_dport */
+#define XFG_QUEUE_NONE 0xffu
+
+struct xfg_steer_queue {        /* one worker's TX ring */
+	void *tx_descs;
+	uint32_t tx_first, tx_mask;
+};
+
+struct xfg_steer {
+	size_t sz;                  /* sizeof(struct xfg_steer), for extension */
+	void *umem;                 /* device; read for every PASS frame, written with SWAP_MACS */
+	const void *rx_descs;
+	uint32_t rx_first, rx_mask;
+	const struct xfg_steer_queue *queues;  /* HOST, nqueues entries */
+	const uint32_t *avail;      /* HOST, navail queue numbers (cpus_available); NULL: identity, navail = nqueues */
+	uint32_t nqueues, navail;   /* navail is cpus_count */
+	uint32_t mode, skip_queue;
+	uint64_t *fill_addrs;       /* NULL: no fill entries written */
+	uint32_t fill_first, fill_mask;
+	uint64_t count;             /* < 2^32 */
+	uint64_t *counts;           /* device, (nqueues + 2) x u64 */
+	uint8_t *queue_of;          /* device, count bytes, or NULL */
+	uint32_t flags;             /* XFG_EGRESS_SWAP_MACS only */
+};
+
+int xfg_steer_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s,
+		     const uint8_t *verdicts, void *stream);
+
+/*
  * Many sockets over one UMEM: one classify and one egress for a whole poll
  * round.  An AF_XDP application has one socket per NIC queue over a shared
  * UMEM (lib/util/xdpsock.c:1788-1809) and peeks a small batch (batch_size 64,

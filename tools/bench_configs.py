@@ -27,6 +27,10 @@
       MAC swap, beside xfg_compact on the same verdicts -- each timed over
       --iters launches between events on a caller stream, with the bytes
       moved and their share of this device's streaming-read rate
+  c3st c3f's batch classified, then steered (xfg_steer_egress): the PASS
+      frames over 1, 8 and 64 workers' TX rings in modes L4_HASH and L4_DPORT,
+      beside xfg_ring_egress on the same batch and verdicts, timed as c3f's
+      legs are; the records a queue gets (least, most) and the refused frames
   c3c  c3d's batch classified, then its DROP frames captured as pcapng blocks
       (xfg_capture_descs, snaplen 0), beside xfg_compact; the same ring with
       1514-byte frames at snaplen 96, one in ten selected; one tile of
@@ -322,6 +326,80 @@ def run_c3f(args):
         gbs = moved[k] / (best * 1e-3) / 1e9
         line[k] = {"ms": [round(m, 4) for m in ms[k]], "bytes": moved[k], "GBps": round(gbs, 1),
                    "frac_of_stream_read": round(gbs / read_gbs, 3)}
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
+def run_c3st(args):
+    """c3f's batch classified, then steered (xfg_steer_egress): the PASS frames
+    over 1, 8 and 64 workers' TX rings by L4_HASH and by L4_DPORT, beside
+    xfg_ring_egress on the same batch and verdicts.  Legs timed as c3f's."""
+    import numpy as np
+    import torch
+    import xfgpu as G
+    w = c3d_workload(args, "c3st")
+    f, n, entries, first = w.f, w.n, w.entries, w.first
+    f.classify_descs(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, first=first, mask=entries - 1)
+    f.sync()
+    npass = int(np.count_nonzero(w.d_verd.download(np.zeros(n, np.uint8)) == 2))
+    kmax = 64
+    d_tx, d_fill, d_c = f.alloc(16 * n * kmax), f.alloc(8 * n), f.alloc(8 * (kmax + 2))
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def egress():
+        f.ring_egress(w.d_descs.ptr, n, w.d_verd.ptr, d_c.ptr, tx_ptr=d_tx.ptr, fill_ptr=d_fill.ptr,
+                      rx_first=first, rx_mask=entries - 1, tx_first=n - 777, tx_mask=n - 1,
+                      fill_first=n - 555, fill_mask=n - 1, stream=sp)
+
+    def steer(k, mode):
+        queues = G.steer_queues([(d_tx.ptr + 16 * n * q, n - 777 + q, n - 1) for q in range(k)])
+        return lambda: f.steer_egress(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, d_c.ptr, queues,
+                                      mode=mode, fill_ptr=d_fill.ptr, rx_first=first,
+                                      rx_mask=entries - 1, fill_first=n - 555, fill_mask=n - 1,
+                                      stream=sp)
+
+    legs = {"ring_egress": egress}
+    for k in (1, 8, 64):
+        legs[f"steer_hash_k{k}"] = steer(k, G.STEER_L4_HASH)
+        legs[f"steer_dport_k{k}"] = steer(k, G.STEER_L4_DPORT)
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            call()
+        e0.record(stream)
+        for _ in range(args.iters):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    runs = max(1, args.runs)
+    ms = {k: [] for k in legs}
+    spread = {}
+    for r in range(runs):      # the legs interleaved
+        for k, call in legs.items():
+            ms[k].append(timed(call))
+            if r == 0 and k != "ring_egress":
+                nq = int(k.rsplit("k", 1)[1])
+                c = d_c.download(np.zeros(nq + 2, np.uint64)).astype(np.int64)
+                assert int(c[:nq].sum()) == npass and int(c[nq]) == n - npass, c
+                spread[k] = {"min": int(c[:nq].min()), "max": int(c[:nq].max()), "refused": int(c[nq + 1])}
+    # bytes the algorithm moves beyond xfg_ring_egress's: the header line (64
+    # bytes) of every PASS frame
+    base = 17 * n + 16 * npass + 8 * (n - npass)
+    line = {"config": "c3st", "program": f.prog_name, "packets": n, "pass_frames": npass,
+            "ring_entries": entries, "umem_chunk": C3D_CHUNK, "iters": args.iters,
+            "setup_s": round(w.setup_s, 1)}
+    ref = min(ms["ring_egress"])
+    for k in legs:
+        best = min(ms[k])
+        moved = base + (0 if k == "ring_egress" else 64 * npass)
+        line[k] = {"ms": [round(m, 4) for m in ms[k]], "bytes": moved,
+                   "GBps": round(moved / (best * 1e-3) / 1e9, 1), "vs_ring_egress": round(best / ref, 2)}
+        if k in spread:
+            line[k]["queue_records"] = spread[k]
     f.close()
     print(json.dumps(line), flush=True)
 
@@ -1103,6 +1181,8 @@ def run(name, args):
         return run_c3d(args)
     if name == "c3f":
         return run_c3f(args)
+    if name == "c3st":
+        return run_c3st(args)
     if name == "c3m":
         return run_c3m(args)
     if name == "c3mc":

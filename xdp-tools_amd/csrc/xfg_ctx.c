@@ -58,6 +58,7 @@ int xfg_launch_socks_egress(const struct xfg_socks_kargs *a, unsigned grid, void
 int xfg_launch_socks_frags_heads(const struct xfg_socks_frags_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *verdicts,
 				  uint32_t n, unsigned grid, void *stream);
+int xfg_launch_steer(const struct xfg_steer_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_frags_egress(const struct xfg_socks_frags_egress_kargs *a, unsigned grid,
 				  void *stream);
 int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
@@ -2549,6 +2550,22 @@ static int socks_check(const struct xfg_socks *sk, uint64_t *total)
 	return 0;
 }
 
+/* Staging slot @k, allocated on first use, once its last user -- SOCKS_SLOTS
+ * calls ago -- is done (d->lock held, the device current). */
+static int socks_slot(struct xfg_dev *d, int k)
+{
+	int err = 0;
+	if (!d->sk_host[k])
+		HIPCHK(hipHostMalloc((void **)&d->sk_host[k], SOCKS_SLOT_BYTES, hipHostMallocDefault));
+	if (!d->sk_dev[k])
+		HIPCHK(hipMalloc((void **)&d->sk_dev[k], SOCKS_SLOT_BYTES));
+	if (!d->sk_done[k])
+		HIPCHK(hipEventCreateWithFlags(&d->sk_done[k], hipEventDisableTiming));
+	HIPCHK(hipEventSynchronize(d->sk_done[k]));
+fail:
+	return err;
+}
+
 /* The socket table of @sk on its way to the device (d->lock held, the device
  * current): into the next staging slot -- waiting for the slot's last user,
  * SOCKS_SLOTS calls ago, only if that is still in flight -- and from there to
@@ -2563,13 +2580,8 @@ static int socks_table(struct xfg_dev *d, const struct xfg_socks *sk, int *slot,
 {
 	int err = 0;
 	const int k = (int)d->sk_next;
-	if (!d->sk_host[k])
-		HIPCHK(hipHostMalloc((void **)&d->sk_host[k], SOCKS_SLOT_BYTES, hipHostMallocDefault));
-	if (!d->sk_dev[k])
-		HIPCHK(hipMalloc((void **)&d->sk_dev[k], SOCKS_SLOT_BYTES));
-	if (!d->sk_done[k])
-		HIPCHK(hipEventCreateWithFlags(&d->sk_done[k], hipEventDisableTiming));
-	HIPCHK(hipEventSynchronize(d->sk_done[k]));
+	if ((err = socks_slot(d, k)))
+		return err;
 	struct xfg_sock_ent *he = (struct xfg_sock_ent *)d->sk_host[k];
 	uint32_t *hb = (uint32_t *)(he + sk->nsocks);
 	uint32_t n = 0;
@@ -2762,6 +2774,99 @@ int xfg_socks_egress(xfg_ctx *ctx, int dev, const struct xfg_socks *sk,
 		     const struct xfg_socks_egress *e, const uint8_t *verdicts, void *stream)
 {
 	return socks_egress(ctx, dev, sk, e, NULL, verdicts, stream, 0);
+}
+
+/* Steered egress (include/xdpfilter_gpu.h): the queues' rings and the avail
+ * table reach the device as the socket tables do, through the next staging
+ * slot, so the call makes no host synchronisation. */
+_Static_assert(XFG_STEER_QUEUES_MAX == XFG_STEER_QUEUES && XFG_STEER_AVAIL_MAX == XFG_STEER_AVAIL &&
+	       XFG_QUEUE_NONE == XFG_STEER_NONE, "the kernel's tables");
+_Static_assert(XFG_STEER_L4_HASH == XFG_STEER_MODE_HASH && XFG_STEER_L4_SPORT == XFG_STEER_MODE_SPORT &&
+	       XFG_STEER_L4_DPORT == XFG_STEER_MODE_DPORT, "the kernel's modes");
+_Static_assert(XFG_STEER_TABLE_BYTES(XFG_STEER_QUEUES, XFG_STEER_AVAIL) <= SOCKS_SLOT_BYTES,
+	       "a staging slot holds the table");
+
+struct steer_job {
+	const struct xfg_steer *s;
+	struct xfg_steer_kargs a;
+};
+
+static int steer_go(struct xfg_dev *d, unsigned grid, void *arg)
+{
+	struct steer_job *j = arg;
+	const struct xfg_steer *s = j->s;
+	struct xfg_steer_kargs *a = &j->a;
+	const int k = (int)d->sk_next;
+	int err = socks_slot(d, k);
+	if (err)
+		return err;
+	struct xfg_sock_ring *hq = (struct xfg_sock_ring *)d->sk_host[k];
+	uint8_t *ha = (uint8_t *)(hq + a->nqueues);
+	for (uint32_t q = 0; q < a->nqueues; q++)
+		hq[q] = (struct xfg_sock_ring){ (uintptr_t)s->queues[q].tx_descs, s->queues[q].tx_first,
+						s->queues[q].tx_mask };
+	for (uint32_t i = 0; i < a->navail; i++)
+		ha[i] = (uint8_t)(s->avail ? s->avail[i] : i);
+	HIPCHK(hipMemcpyAsync(d->sk_dev[k], d->sk_host[k], XFG_STEER_TABLE_BYTES(a->nqueues, a->navail),
+			      hipMemcpyHostToDevice, d->stream));
+	d->sk_next = (uint32_t)(k + 1) % SOCKS_SLOTS;
+	a->queues = (const struct xfg_sock_ring *)d->sk_dev[k];
+	a->avail = (const uint8_t *)(a->queues + a->nqueues);
+	a->state = d->cstatus;
+	err = xfg_launch_steer(a, grid, d->stream);
+	return socks_table_done(d, k, err);
+fail:
+	return err;
+}
+
+int xfg_steer_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s, const uint8_t *verdicts,
+		     void *stream)
+{
+	int err;
+	if (!ctx || !s || s->sz < sizeof(*s) || !s->queues || !s->nqueues ||
+	    s->nqueues > XFG_STEER_QUEUES_MAX || s->skip_queue >= s->nqueues ||
+	    s->mode > XFG_STEER_L4_DPORT || (s->flags & ~XFG_EGRESS_SWAP_MACS) ||
+	    s->count > 0xffffffffull || !s->counts)
+		return -EINVAL;
+	const uint32_t navail = s->avail ? s->navail : s->nqueues;
+	if (!navail || navail > XFG_STEER_AVAIL_MAX)
+		return -EINVAL;
+	if (!mask_ok(s->rx_mask) || (s->fill_addrs && !mask_ok(s->fill_mask)))
+		return -EINVAL;
+	if (((uintptr_t)s->umem & 7) || ((uintptr_t)s->rx_descs & 7) || ((uintptr_t)s->fill_addrs & 7) ||
+	    ((uintptr_t)s->counts & 7))
+		return -EINVAL;
+	if (s->fill_addrs && (uint64_t)s->fill_mask + 1 < s->count)
+		return -EINVAL;
+	/* a ring that can be written: one an avail entry or skip_queue names */
+	for (uint32_t i = 0; i <= navail; i++) {
+		const uint32_t q = i == navail ? s->skip_queue : s->avail ? s->avail[i] : i;
+		if (q >= s->nqueues)
+			return -EINVAL;
+		const struct xfg_steer_queue *k = &s->queues[q];
+		if (!k->tx_descs || ((uintptr_t)k->tx_descs & 7) || !mask_ok(k->tx_mask) ||
+		    (uint64_t)k->tx_mask + 1 < s->count)
+			return -EINVAL;
+	}
+	if (s->count && (!s->umem || !s->rx_descs || !verdicts))
+		return -EINVAL;
+	if ((err = dev_check(ctx, dev)))
+		return err;
+	struct steer_job j = {
+		.s = s,
+		.a = {
+			.umem = s->umem, .rx = s->rx_descs, .fill = s->fill_addrs, .verdicts = verdicts,
+			.queue_of = s->queue_of, .counts = (unsigned long long *)s->counts,
+			.rx_first = s->rx_first, .rx_mask = s->rx_mask,
+			.fill_first = s->fill_first, .fill_mask = s->fill_mask,
+			.n = (uint32_t)s->count, .nqueues = s->nqueues, .navail = navail,
+			.mode = s->mode, .skip_queue = s->skip_queue,
+			.swap_macs = !!(s->flags & XFG_EGRESS_SWAP_MACS),
+		},
+	};
+	return scratch_launch(&ctx->dev[dev], stream, s->count ? NULL : s->counts,
+			      ((size_t)s->nqueues + 2) * 8, XFG_STEER_STATE_WORDS(s->count, s->nqueues),
+			      steer_go, &j);
 }
 
 /* Multi-buffer batches of many sockets (include/xdpfilter_gpu.h), a staged

@@ -2221,4 +2221,8 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // egress with a per-socket count of records in complete packets
 #include "xfg_socks_frags.hip"
 
+// steered egress (PASS frames over K workers' TX rings by flow): the egress
+// kernel's scheme with K sums a tile and a wave-wide look-back
+#include "xfg_steer.hip"
+
 #endif   // XFG_PART_COMMON

@@ -562,6 +562,45 @@ struct xfg_socks_frags_egress_kargs {
 #define XFG_SOCKS_FRAGS_TABLE_BYTES(nsocks) \
 	(XFG_SOCKS_TABLE_BYTES(nsocks) + (2 * (uint64_t)(nsocks) + 1) * 4)
 
+/* Steered egress (xfg_steer.hip, xfg_steer_egress()): an order-preserving
+ * K-way partition of the PASS records over the workers' TX rings.  A launch's
+ * table in device memory (a staging slot of the socket calls) is the nqueues
+ * TX rings, one struct xfg_sock_ring each, and behind them the navail queue
+ * numbers of the avail table, a byte each.  The state words: word 0 the tile
+ * ticket, word 1 padding, from word 2 the tiles' status words, nqueues a tile
+ * (tile t's word of queue q at XFG_STEER_STATUS(t, nqueues) + q; zeroed by the
+ * launch function, as counts[nqueues + 1] is, which the tiles add to). */
+struct xfg_steer_kargs {
+	uint8_t *umem;                  /* read for every PASS frame, written with swap_macs */
+	const void *rx;
+	const struct xfg_sock_ring *queues;   /* the table */
+	const uint8_t *avail;           /* behind it */
+	uint64_t *fill;                 /* NULL: none written */
+	const uint8_t *verdicts;
+	uint8_t *queue_of;              /* NULL: not written */
+	unsigned long long *counts;     /* nqueues + 2 */
+	unsigned long long *state;
+	uint32_t rx_first, rx_mask;
+	uint32_t fill_first, fill_mask;
+	uint32_t n;                     /* records, >= 1 */
+	uint32_t nqueues, navail;
+	uint32_t mode, skip_queue;
+	uint32_t swap_macs;
+};
+#define XFG_STEER_QUEUES 64u    /* XFG_STEER_QUEUES_MAX: a lane a queue in the look-back */
+#define XFG_STEER_AVAIL 256u    /* XFG_STEER_AVAIL_MAX: the table in LDS, a lane an entry */
+#define XFG_STEER_NONE 0xffu    /* XFG_QUEUE_NONE */
+#define XFG_STEER_MODE_HASH 0u   /* XFG_STEER_L4_HASH, _SPORT, _DPORT */
+#define XFG_STEER_MODE_SPORT 1u
+#define XFG_STEER_MODE_DPORT 2u
+#define XFG_STEER_TILE 2048u    /* records a tile: 256 lanes x 8 passes */
+#define XFG_STEER_TILES(n) (((uint64_t)(n) + XFG_STEER_TILE - 1) / XFG_STEER_TILE)
+#define XFG_STEER_STATUS(t, nqueues) (2 + (uint64_t)(t) * (nqueues))
+/* (an even count: the launch's one memset is then a multiple of 16 bytes) */
+#define XFG_STEER_STATE_WORDS(n, nqueues) ((XFG_STEER_STATUS(XFG_STEER_TILES(n), nqueues) + 1) & ~1ull)
+#define XFG_STEER_TABLE_BYTES(nqueues, navail) \
+	((uint64_t)(nqueues) * sizeof(struct xfg_sock_ring) + (uint64_t)(navail))
+
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 #define XFG_HD __host__ __device__ __forceinline__

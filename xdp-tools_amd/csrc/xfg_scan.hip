@@ -11,7 +11,8 @@
 // runs.  A ballot ranks an item in its wave and pass (xfg_wave_rank()), an
 // LDS step over the (pass, wave) counts in the tile (xfg_tile_step()), and
 // one lane's decoupled look-back over the earlier tiles' status words gives
-// the tile's base (xfg_lookback()).  Kernels that sum bytes instead of
+// the tile's base (xfg_lookback(); xfg_lookback_wave() for a tile with K
+// sums, a lane a sum).  Kernels that sum bytes instead of
 // counting a predicate bring their own wave scan and use the ticket and the
 // look-back.
 //
@@ -151,6 +152,47 @@ __device__ __forceinline__ unsigned long long xfg_lookback(unsigned long long *s
 		__builtin_amdgcn_s_sleep(1);   // predecessor still counting
 	}
 	__hip_atomic_store(&status[t], CT_INC | (base + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	return base;
+}
+
+// The look-back over @nq running sums at once, by one wave (the K-way
+// partition, xfg_steer.hip): a tile has @nq status words in a row, tile p's
+// word of sum q at status[p * nq + q], and lane @q < @nq of the calling wave
+// walks sum q's column as xfg_lookback() walks its one -- the tile's aggregate
+// published at once, the earlier tiles' collected back to the first inclusive
+// word, the tile's own inclusive sum published -- every lane at its own pace,
+// so a column whose predecessor is late holds up no other; the lanes' loads of
+// one tile's words are one contiguous run.  Returns the lane's exclusive base
+// (0 for a lane >= @nq).
+__device__ __forceinline__ unsigned long long xfg_lookback_wave(unsigned long long *status, uint32_t nq,
+								uint32_t t, uint32_t q,
+								unsigned long long agg)
+{
+	if (q >= nq)
+		return 0;
+	unsigned long long *col = status + q;
+	if (t == 0) {
+		__hip_atomic_store(&col[0], CT_INC | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		return 0;
+	}
+	__hip_atomic_store(&col[(uint64_t)t * nq], CT_AGG | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	unsigned long long base = 0;
+	for (uint32_t p = t - 1;;) {
+		const unsigned long long w = __hip_atomic_load(&col[(uint64_t)p * nq], __ATOMIC_RELAXED,
+							       __HIP_MEMORY_SCOPE_AGENT);
+		if (w & CT_INC) {
+			base += w & CT_VAL;
+			break;
+		}
+		if (w & CT_AGG) {
+			base += w & CT_VAL;
+			p--;   // tile 0 always publishes CT_INC
+			continue;
+		}
+		__builtin_amdgcn_s_sleep(1);   // predecessor still counting
+	}
+	__hip_atomic_store(&col[(uint64_t)t * nq], CT_INC | (base + agg), __ATOMIC_RELAXED,
+			   __HIP_MEMORY_SCOPE_AGENT);
 	return base;
 }
 

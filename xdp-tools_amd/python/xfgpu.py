@@ -67,6 +67,7 @@ EXPORTS = [
     "xfg_classify_socks_frags", "xfg_socks_frags_egress", "xfg_capture_descs_frags",
     "xfg_classify_chain", "xfg_classify_descs_chain", "xfg_classify_descs_chain_timed",
     "xfg_classify_descs_frags_chain", "xfg_classify_descs_frags_chain_timed",
+    "xfg_steer_egress",
 ]
 CAPTURE_HEAD_ONLY = 1        # XFG_CAPTURE_HEAD_ONLY
 SOCKS_MAX = 1024
@@ -74,6 +75,9 @@ VERDICT_NONE = 0xff          # XFG_VERDICT_NONE
 PKT_NONE = 0xffffffff        # XFG_PKT_NONE
 EGRESS_SWAP_MACS = 1
 EGRESS_MULTIBUF = 4
+STEER_QUEUES_MAX, STEER_AVAIL_MAX = 64, 256      # XFG_STEER_QUEUES_MAX, XFG_STEER_AVAIL_MAX
+STEER_L4_HASH, STEER_L4_SPORT, STEER_L4_DPORT = 0, 1, 2
+QUEUE_NONE = 0xff            # XFG_QUEUE_NONE
 XDP_PKT_CONTD = 1
 XDP_ABORTED, XDP_DROP, XDP_PASS = 0, 1, 2
 CHAIN_PASS = 1 << XDP_PASS   # XFG_CHAIN_PASS
@@ -116,6 +120,37 @@ class Egress(C.Structure):
                 ("tx_descs", C.c_void_p), ("tx_first", C.c_uint32), ("tx_mask", C.c_uint32),
                 ("fill_addrs", C.c_void_p), ("fill_first", C.c_uint32), ("fill_mask", C.c_uint32),
                 ("count", C.c_uint64), ("counts", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class SteerQueue(C.Structure):
+    """struct xfg_steer_queue: one worker's TX ring."""
+    _fields_ = [("tx_descs", C.c_void_p), ("tx_first", C.c_uint32), ("tx_mask", C.c_uint32)]
+
+
+class Steer(C.Structure):
+    """struct xfg_steer (xfg_steer_egress)."""
+    _fields_ = [("sz", C.c_size_t), ("umem", C.c_void_p),
+                ("rx_descs", C.c_void_p), ("rx_first", C.c_uint32), ("rx_mask", C.c_uint32),
+                ("queues", C.POINTER(SteerQueue)), ("avail", C.POINTER(C.c_uint32)),
+                ("nqueues", C.c_uint32), ("navail", C.c_uint32),
+                ("mode", C.c_uint32), ("skip_queue", C.c_uint32),
+                ("fill_addrs", C.c_void_p), ("fill_first", C.c_uint32), ("fill_mask", C.c_uint32),
+                ("count", C.c_uint64), ("counts", C.c_void_p), ("queue_of", C.c_void_p),
+                ("flags", C.c_uint32)]
+
+
+def steer_queues(queues):
+    """A host queue table (a ctypes array of SteerQueue) from SteerQueue values
+    or (tx_ptr, tx_first, tx_mask) triples; a bare pointer is a plain array."""
+    arr = (SteerQueue * max(len(queues), 1))()
+    for i, q in enumerate(queues):
+        if isinstance(q, SteerQueue):
+            arr[i] = q
+        elif isinstance(q, (tuple, list)):
+            arr[i] = SteerQueue(*q)
+        else:
+            arr[i] = SteerQueue(q, 0, 0xffffffff)
+    return arr
 
 
 class Frags(C.Structure):
@@ -256,6 +291,7 @@ def _load():
         "xfg_compact": (C.c_int, [vp, C.c_int, vp, C.c_uint64, C.c_uint32, vp, vp, vp]),
         "xfg_ring_egress": (C.c_int, [vp, C.c_int, C.POINTER(Egress), vp, vp]),
         "xfg_classify_socks": (C.c_int, [vp, C.c_int, C.POINTER(Socks), vp, vp]),
+        "xfg_steer_egress": (C.c_int, [vp, C.c_int, C.POINTER(Steer), vp, vp]),
         "xfg_socks_egress": (C.c_int, [vp, C.c_int, C.POINTER(Socks), C.POINTER(SocksEgress), vp,
                                        vp]),
         "xfg_classify_socks_frags": (C.c_int, [vp, C.c_int, C.POINTER(Socks),
@@ -719,6 +755,25 @@ class Filter:
                    tx_mask, fill_ptr, fill_first, fill_mask, count, counts_ptr, flags)
         _check(lib.xfg_ring_egress(self.ctx, dev, C.byref(e), verdicts_ptr, stream),
                "ring_egress")
+
+    def steer_egress(self, umem_ptr, rx_ptr, count, verdicts_ptr, counts_ptr, queues, avail=None,
+                     mode=STEER_L4_HASH, skip_queue=0, nqueues=None, fill_ptr=None, rx_first=0,
+                     rx_mask=0xffffffff, fill_first=0, fill_mask=0xffffffff, queue_of_ptr=None,
+                     flags=0, dev=0, stream=None):
+        """The PASS frames of an RX descriptor batch over the workers' TX rings
+        by flow, the others' chunks to the fill ring (xfg_steer_egress).
+        queues: a host table from steer_queues() (or what it takes); avail: the
+        queue numbers the hash or port indexes (None: the identity); counts_ptr:
+        nqueues + 2 u64 on the device.  Both tables may be overwritten as soon
+        as this returns."""
+        tab = queues if isinstance(queues, C.Array) else steer_queues(queues)
+        av = None if avail is None else (C.c_uint32 * max(len(avail), 1))(*[int(a) for a in avail])
+        s = Steer(C.sizeof(Steer), umem_ptr, rx_ptr, rx_first, rx_mask, tab, av,
+                  len(queues) if nqueues is None else nqueues, 0 if avail is None else len(avail),
+                  mode, skip_queue, fill_ptr, fill_first, fill_mask, count, counts_ptr,
+                  queue_of_ptr, flags)
+        _check(lib.xfg_steer_egress(self.ctx, dev, C.byref(s), verdicts_ptr, stream),
+               "steer_egress")
 
     def classify_socks(self, umem_ptr, socks, verdicts_ptr, nsocks=None, flat_ptr=None, dev=0,
                        stream=None):
