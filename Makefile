@@ -5,7 +5,7 @@
 #   tools/plan_replay                      the launch plan over recorded cases (tests, CPU only)
 #   oracle/build/liboracle.so              CPU restatement (tests / bench cpu_baseline)
 #   oracle/_ref/libref_<variant>.so        the reference's own programs for the host (tests;
-#                                          only where the reference tree is present)
+#   oracle/_ref/libref_cpumap.so           only where the reference tree is present)
 # `make asan` builds the host C (restatement, runtime, I/O, CLI) under ASAN +
 # UBSAN for the CPU suite's sanitizer run (tools/asan_suite.sh).
 JOBS ?= 8

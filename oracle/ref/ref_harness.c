@@ -16,7 +16,8 @@
  *   - per-CPU maps: one CPU.
  *   - struct xdp_md's 32-bit data/data_end: every frame is copied into an
  *     arena below 4 GiB so that it ends exactly where a PROT_NONE page
- *     begins; a read past data_end by the program faults here, on the CPU.
+ *     begins; a read past data_end by the program faults here, on the CPU
+ *     (ref_arena.h, shared with ref_cpumap_harness.c).
  *
  * Not thread-safe (one arena, one set of map bindings): call from one thread.
  */
@@ -24,8 +25,6 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/mman.h>
-#include <unistd.h>
 
 #ifndef VARIANT_C
 #error "compile with -DVARIANT_C='\"xdpfilt_<variant>.c\"'"
@@ -136,33 +135,7 @@ void *ref_map_lookup(const void *map_ptr, const void *key_ptr,
 }
 
 /* ---------------- frame arena below 4 GiB, guard page behind it ---------- */
-static uint8_t *g_arena;
-static size_t g_arena_len; /* bytes in front of the guard page */
-
-static int ref_arena_reserve(size_t need)
-{
-	size_t page = (size_t)sysconf(_SC_PAGESIZE);
-	size_t len = (need + page - 1) / page * page;
-	if (!len)
-		len = page;
-	if (g_arena && g_arena_len >= len)
-		return 0;
-	if (g_arena)
-		munmap(g_arena, g_arena_len + page);
-	g_arena = NULL;
-	void *p = mmap(NULL, len + page, PROT_READ | PROT_WRITE,
-		       MAP_PRIVATE | MAP_ANONYMOUS | MAP_32BIT, -1, 0);
-	if (p == MAP_FAILED)
-		return -1;
-	if ((uintptr_t)p + len + page > (1ull << 32) ||
-	    mprotect((char *)p + len, page, PROT_NONE)) {
-		munmap(p, len + page);
-		return -1;
-	}
-	g_arena = p;
-	g_arena_len = len;
-	return 0;
-}
+#include "ref_arena.h"
 
 uint32_t ref_features(void)
 {

@@ -3,8 +3,11 @@ queue a PASS frame takes, the K-way order-preserving partition and the counts.
 
 The queue choice follows xdp-bench redirect-cpu's programs; every rule names
 the lines of the reference's xdp-bench/xdp_redirect_cpumap.bpf.c (":N" below)
-or xdp-bench/hash_func01.h it models.  Frames are bytes objects; nothing here
-is fast, and nothing needs to be.
+or xdp-bench/hash_func01.h it models.  The citations are a reader's aid, not
+the proof: tests/test_steer_reference.py holds queue_of_frame() equal to those
+programs themselves, compiled for the host and run (oracle/ref/
+ref_cpumap_harness.c), over tests/steercorpus.py and 100,000 random frames.
+Frames are bytes objects; nothing here is fast, and nothing needs to be.
 """
 import numpy as np
 

@@ -2,10 +2,13 @@
 batch over K workers' TX rings by flow, the other frames' chunks to the fill
 ring.
 
-Every comparison is exact against tests/steermodel.py (pinned by the CPU tests
-to the reference's programs).  A case's frames are a pool of distinct frames in
-a UMEM of random bytes -- so a byte read past a frame's len changes a hash --
-and records that name them; every TX ring, the fill ring, queue_of and counts
+Every comparison is exact against tests/steermodel.py, which
+test_steer_reference.py holds equal to the reference's own redirect-cpu
+programs run on the host (oracle/ref/ref_cpumap_harness.c) over a corpus and
+100,000 random frames; test_gpu_steer_reference.py beside this file takes its
+expected values from that run directly.  A case's frames are a pool of
+distinct frames in a UMEM of random bytes -- so a byte read past a frame's len
+changes a hash -- and records that name them; every TX ring, the fill ring, queue_of and counts
 are uploaded as 0xA5 bytes and compared whole against a copy with the expected
 entries written in, so entries nothing should reach must come back untouched.
 """
@@ -18,7 +21,7 @@ import pytest
 
 import steermodel as M
 import xftools as X
-from test_gpu_egress import A5, Rings, slots
+from test_gpu_egress import A5, Rings, pow2_at_least, slots
 
 pytestmark = pytest.mark.gpu
 
@@ -126,14 +129,24 @@ def verdicts_of(n, pattern):
 def run_steer(G, f, pool, fid, v, nq, mode=M.L4_HASH, avail=None, skip_queue=0, kind="array",
               rot=0, fill=True, queue_of=True, flags=0, seed=3, precheck=None):
     """One call over the records fid (indices into pool) with verdicts v;
-    checks counts, every ring, queue_of and the UMEM whole."""
-    n = len(fid)
+    checks counts, every ring, queue_of and the UMEM whole against the model."""
     umem, paddr, pstart, plens = umem_of_pool(pool, seed)
     addr, lens = paddr[fid], plens[fid]
-    want_tx, want_fill, want_counts, want_qof = M.steer_model(pool, addr, lens, v, nq, mode, avail,
-                                                              skip_queue, fid=fid)
+    want = M.steer_model(pool, addr, lens, v, nq, mode, avail, skip_queue, fid=fid)
     if precheck:
-        precheck(want_counts)
+        precheck(want[2])
+    return check_steer(G, f, umem, addr, pstart[fid], lens, v, nq, want, mode=mode, avail=avail,
+                       skip_queue=skip_queue, kind=kind, rot=rot, fill=fill, queue_of=queue_of, flags=flags)
+
+
+def check_steer(G, f, umem, addr, start, lens, v, nq, want, mode=M.L4_HASH, avail=None, skip_queue=0,
+                kind="array", rot=0, fill=True, queue_of=True, flags=0):
+    """One call over the records (addr, lens) with verdicts v, record i's frame
+    at umem[start[i]]; checks counts, every ring, queue_of and the UMEM whole
+    against @want = (tx, fill, counts, queue_of) as steermodel.steer_model
+    returns them, wherever they come from."""
+    n = len(v)
+    want_tx, want_fill, want_counts, want_qof = want
     rings = Rings(n, kind, rot)
     rx_e, tx_e, fill_e = rings.entries
     rx_h = np.full((max(rx_e, 1), 2), A5, np.uint64)
@@ -185,7 +198,7 @@ def run_steer(G, f, pool, fid, v, nq, mode=M.L4_HASH, avail=None, skip_queue=0, 
     want_umem = umem
     if flags & G.EGRESS_SWAP_MACS:
         want_umem = umem.copy()
-        at = pstart[fid[v == PASS]][:, None] + np.arange(12)
+        at = np.asarray(start)[v == PASS][:, None] + np.arange(12)
         want_umem[at] = umem[at][:, [6, 7, 8, 9, 10, 11, 0, 1, 2, 3, 4, 5]]
     np.testing.assert_array_equal(got_umem, want_umem)
     return want_counts
@@ -344,14 +357,16 @@ def classified(G):
     f.close()
 
 
-def check_after_classify(f, classified_case, nq, mode, launch):
+def check_after_classify(f, classified_case, nq, mode, launch, want=None):
     """@launch(d_u, d_rx, d_v) classifies; then one steer call on the same
-    stream with nothing in between, and everything compared."""
+    stream with nothing in between, and everything compared: with the model's
+    answer for the verdicts ov, or with @want in its place."""
     _, umem, addr, lens, frames, ov = classified_case
     n = len(lens)
-    want_tx, want_fill, want_counts, want_qof = M.steer_model(frames, addr, lens, ov, nq, mode, None, 0)
-    tx_h = np.full((nq, 8192, 2), A5, np.uint64)
-    fill_h = np.full(8192, A5, np.uint64)
+    E = max(8192, pow2_at_least(n))      # entries a ring
+    want_tx, want_fill, want_counts, want_qof = want or M.steer_model(frames, addr, lens, ov, nq, mode, None, 0)
+    tx_h = np.full((nq, E, 2), A5, np.uint64)
+    fill_h = np.full(E, A5, np.uint64)
     cnt_h = np.full(nq + 3, A5, np.uint64)
     qof_h = np.full(n + 16, 0xA5, np.uint8)
     descs = np.empty((n, 2), np.uint64)
@@ -365,9 +380,9 @@ def check_after_classify(f, classified_case, nq, mode, launch):
         d_v.upload(np.zeros(n, np.uint8))
         f.sync()
         rx_ptr, sp = launch(d_u, d_rx, d_v)
-        queues = [(d_tx.ptr + q * tx_h[0].nbytes, 8192 - 100 + q, 8191) for q in range(nq)]
+        queues = [(d_tx.ptr + q * tx_h[0].nbytes, E - 100 + q, E - 1) for q in range(nq)]
         f.steer_egress(d_u.ptr, rx_ptr, n, d_v.ptr, d_c.ptr, queues, mode=mode, fill_ptr=d_fill.ptr,
-                       fill_first=0xfffffff0, fill_mask=8191, queue_of_ptr=d_qof.ptr, stream=sp)
+                       fill_first=0xfffffff0, fill_mask=E - 1, queue_of_ptr=d_qof.ptr, stream=sp)
         if sp:
             import torch
             torch.cuda.synchronize()
@@ -378,8 +393,8 @@ def check_after_classify(f, classified_case, nq, mode, launch):
         qof_h[:n] = want_qof
         np.testing.assert_array_equal(d_qof.download(np.zeros_like(qof_h)), qof_h)
         for q in range(nq):
-            tx_h[q][slots(8192 - 100 + q, len(want_tx[q]), 8191)] = want_tx[q]
-        fill_h[slots(0xfffffff0, len(want_fill), 8191)] = want_fill
+            tx_h[q][slots(E - 100 + q, len(want_tx[q]), E - 1)] = want_tx[q]
+        fill_h[slots(0xfffffff0, len(want_fill), E - 1)] = want_fill
         np.testing.assert_array_equal(d_tx.download(np.zeros_like(tx_h)), tx_h)
         np.testing.assert_array_equal(d_fill.download(np.zeros_like(fill_h)), fill_h)
     finally:

@@ -1,7 +1,9 @@
 """CPU tests that pin tests/steermodel.py, the model the GPU tests of
 xfg_steer_egress compare against: the hash against known answers and against
 the reference's own header, the queue choice against hand-written rows (one a
-branch of the reference's programs), the partition against a per-record walk."""
+branch of the reference's programs), the partition against a per-record walk.
+The rows' answers (WANT) were written by hand; test_steer_reference.py
+recomputes them from the reference's programs run on the host."""
 import os
 import re
 import shutil

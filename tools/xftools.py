@@ -5,6 +5,7 @@ ctypes bindings for:
   * oracle/build/liboracle.so  our CPU restatement of the xdpfilt_* program
   * oracle/_ref/libref_*.so    the reference's own xdpfilt_*.c, compiled for the
                                host (oracle/ref/; tests only)
+  * oracle/_ref/libref_cpumap.so  the reference's redirect-cpu programs, likewise
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use the
 oracle binding, and only as the checker / the CPU baseline.
@@ -328,3 +329,59 @@ def run_reference(variant, data, lens, rules: RuleSet, stride=0, offsets=None, s
     if rc:
         raise RuntimeError("reference run failed (no arena below 4 GiB?)")
     return verdicts, r, st.reshape(5, 2)
+
+
+# ----------------------------------------------------------------- reference, redirect-cpu
+STEER_HASH, STEER_SPORT, STEER_DPORT = 0, 1, 2      # XFG_STEER_L4_*; ref_cpumap_harness.c's modes
+XDP_ABORTED, XDP_PASS, XDP_REDIRECT = 0, 2, 4
+_ref_cpumap = None
+
+
+def _ref_cpumap_path():
+    return os.path.join(REF_DIR, "libref_cpumap.so")
+
+
+def have_reference_steer() -> bool:
+    """True when the host build of the reference's redirect-cpu programs is present."""
+    return os.path.exists(_ref_cpumap_path())
+
+
+def reference_steer():
+    """The host build of the reference's xdp_redirect_cpumap.bpf.c (oracle/ref/)."""
+    global _ref_cpumap
+    if _ref_cpumap is None:
+        lib = C.CDLL(_ref_cpumap_path())
+        lib.ref_cpumap_nr_cpus.restype = C.c_uint32
+        lib.ref_cpumap_nr_cpus.argtypes = []
+        lib.ref_cpumap_run.argtypes = [_u8p, _u64p, C.c_uint32, _u32p, C.c_uint64, C.c_uint32,
+                                       _u32p, C.c_uint32, _u8p, _u32p, _u64p]
+        _ref_cpumap = lib
+    return _ref_cpumap
+
+
+def run_reference_steer(data, lens, mode, avail, skip_queue=0, stride=0, offsets=None, rec=None):
+    """Run the reference's cpumap_l4_hash / _sport / _dport (mode STEER_*) with
+    cpus_available = avail and cpus_count = len(avail), in xfg_steer_egress's
+    terms: returns (queue, refused), a queue number and a flag per frame.
+    XDP_REDIRECT: the queue is the key the program redirected to.  XDP_PASS
+    (parse_eth refused the frame): skip_queue, refused.  XDP_ABORTED -- an
+    avail entry at or above nr_cpus, which xfg_steer_egress refuses with
+    -EINVAL as an entry at or above nqueues -- must not occur and raises.
+    rec (u64[2], optional) accumulates rx_cnt's processed and issue."""
+    lib = reference_steer()
+    n = len(lens)
+    data = np.ascontiguousarray(data, np.uint8)
+    lens = np.ascontiguousarray(lens, np.uint32)
+    offs = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
+    av = np.ascontiguousarray(avail, np.uint32)
+    rcs = np.zeros(n, np.uint8)
+    keys = np.zeros(n, np.uint32)
+    rec = np.zeros(2, np.uint64) if rec is None else rec
+    if lib.ref_cpumap_run(ptr(data), ptr(offs, _u64p), stride, ptr(lens, _u32p), n, mode,
+                          ptr(av, _u32p), len(av), ptr(rcs), ptr(keys, _u32p), ptr(rec, _u64p)):
+        raise RuntimeError("reference run failed (mode, empty avail table, or no arena below 4 GiB)")
+    redirect = rcs == XDP_REDIRECT
+    if not (redirect | (rcs == XDP_PASS)).all():
+        bad = int(np.flatnonzero(~(redirect | (rcs == XDP_PASS)))[0])
+        raise RuntimeError(f"reference returned {int(rcs[bad])} for frame {bad}: an avail entry >= nr_cpus?")
+    return np.where(redirect, keys, skip_queue).astype(np.uint32), ~redirect
