@@ -679,10 +679,13 @@ int xfg_ring_egress(xfg_ctx *ctx, int dev, const struct xfg_egress *e,
  * host-only context (after these checks; no device pointer is dereferenced
  * before it).
  *
- * Not covered: multi-buffer packets (XFG_EGRESS_MULTIBUF is refused: a
- * packet's records would have to follow its head's queue), the host-memory
- * path (xfg_classify_xsk_host), the CLI, and the program's round-robin,
- * l4-proto and l4-filter modes.
+ * Multi-buffer packets (XDP_USE_SG sockets) take xfg_steer_frags_egress below:
+ * this call refuses XFG_EGRESS_MULTIBUF, and must not be used on such a batch
+ * (it would hash a continuation record as if it began with an Ethernet header
+ * and scatter a packet's records over several rings).
+ *
+ * Not covered: the host-memory path (xfg_classify_xsk_host), the CLI, and the
+ * program's round-robin, l4-proto and l4-filter modes.
  */
 #define XFG_STEER_QUEUES_MAX 64u
 #define XFG_STEER_AVAIL_MAX  256u
@@ -710,11 +713,68 @@ struct xfg_steer {
 	uint64_t count;             /* < 2^32 */
 	uint64_t *counts;           /* device, (nqueues + 2) x u64 */
 	uint8_t *queue_of;          /* device, count bytes, or NULL */
-	uint32_t flags;             /* XFG_EGRESS_SWAP_MACS only */
+	uint32_t flags;             /* XFG_EGRESS_SWAP_MACS only (xfg_steer_frags_egress: XFG_EGRESS_MULTIBUF too) */
 };
 
 int xfg_steer_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s,
 		     const uint8_t *verdicts, void *stream);
+
+/*
+ * Steered egress of multi-buffer packets: every record of a packet follows
+ * its head record's queue.  The structure, the queue choice (parse_eth, the
+ * three modes, avail, skip_queue), the tables' staging and the stream ordering
+ * are xfg_steer_egress's, bit for bit; what differs is what a record is part
+ * of.  An XDP program sees only a packet's first buffer, so the head's queue
+ * is what cpumap_l4_hash / _sport / _dport return on the head buffer.
+ *
+ * Packets are formed as xfg_capture_descs_frags forms them.  With v[i] the
+ * verdict byte and o[i] the options of record i:
+ *   live[i] = v[i] != XFG_VERDICT_NONE
+ *   eop[i]  = !(o[i] & XFG_XDP_PKT_CONTD)
+ *   head[i] = live[i] && (i == 0 || !live[i-1] || eop[i-1])
+ * and a live record belongs to the nearest head at or before it.  So one call
+ * serves the output of xfg_classify_descs_frags (count = its counts[1]) and,
+ * as a plain array, sk->flat of xfg_classify_socks_frags, whose
+ * XFG_VERDICT_NONE bytes keep the sockets apart and mark the trailing
+ * incomplete packets.  Both leave every live run ending in an end-of-packet
+ * record; this call does not check that: a live run without one is steered by
+ * its head like any other.  A packet's record count is not limited.
+ *
+ * The head decides the whole packet.  A packet whose head byte is
+ * XFG_XDP_PASS takes the queue xfg_steer_egress would give the head record's
+ * frame (bytes [0, len) at the head's address), and every live record of it
+ * goes to that queue's TX ring; a packet whose head byte is anything else
+ * hands every live record's chunk to the fill ring.  The other records' verdict
+ * bytes count for liveness only, and no UMEM byte of a record that is not a
+ * PASS head is read.
+ *
+ * The k-th live record in record order that takes queue q becomes
+ * queues[q].tx_descs[(tx_first + k) & tx_mask]: addr and len as received,
+ * options = the RX record's options & XFG_XDP_PKT_CONTD (as xfg_ring_egress
+ * with XFG_EGRESS_MULTIBUF), so a packet's records lie adjacent and in order
+ * on one ring.  The j-th live record on the fill side writes
+ * fill_addrs[(fill_first + j) & fill_mask] = addr & ((1 << 48) - 1)
+ * (fill_addrs == NULL: none written).  A record that is not live produces
+ * nothing -- no TX record, no fill entry, no count: the caller leaves it on
+ * its ring.  counts[q]: the TX records of queue q, per record (as l2fwd's
+ * tx_frags counts); counts[nqueues]: the live records on the fill side;
+ * counts[nqueues + 1]: the PASS packets whose head parse_eth refused, per
+ * packet (their records are among counts[skip_queue]).  queue_of[i]: the
+ * packet's queue for every live record of a PASS packet, XFG_QUEUE_NONE for
+ * every other record, those that are not live included.
+ * XFG_EGRESS_SWAP_MACS touches the head records of PASS packets only.
+ *
+ * flags: XFG_EGRESS_SWAP_MACS, with or without XFG_EGRESS_MULTIBUF (implied
+ * here); every other bit is refused.  If every record is an end of packet and
+ * no byte is XFG_VERDICT_NONE, every output byte equals xfg_steer_egress's.
+ *
+ * -EINVAL: everything xfg_steer_egress refuses, but for XFG_EGRESS_MULTIBUF.
+ * -ENODEV on a host-only context, after these checks; no device pointer is
+ * touched before it.  count == 0: the counts are zeroed and nothing else is
+ * written.  Stream-ordered on @stream, no host synchronisation.
+ */
+int xfg_steer_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s,
+			   const uint8_t *verdicts, void *stream);
 
 /*
  * Many sockets over one UMEM: one classify and one egress for a whole poll

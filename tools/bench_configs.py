@@ -57,6 +57,13 @@
       verdicts (the same payload bytes, three times the blocks) -- timed as
       c3c's legs are, with the bytes moved and their share of the
       streaming-read rate
+  c3mst c3m's batch classified by xfg_classify_descs_frags, then steered by whole
+      packets (xfg_steer_frags_egress): every record of a PASS packet to the TX
+      ring of its head's queue, over 1, 8 and 64 rings in modes L4_HASH and
+      L4_DPORT, beside xfg_ring_egress with XFG_EGRESS_MULTIBUF on the same
+      records and verdicts; and the same records as single-record packets
+      through xfg_steer_egress and xfg_steer_frags_egress (8 rings) -- timed as
+      c3st's legs are
   c3mch c3m's batch, classified by xfg_classify_descs_frags, as the first stage
       of a chain (xfg_classify_descs_frags_chain): half the packets' verdict
       bytes pre-set to PASS, once every other packet and once a contiguous
@@ -643,6 +650,98 @@ def c3m_workload(args, name):
                                  frags_path=frags_path)
 
 
+def run_c3mst(args):
+    """c3m's batch classified by xfg_classify_descs_frags, then steered by whole
+    packets (xfg_steer_frags_egress) over 1, 8 and 64 workers' TX rings by
+    L4_HASH and by L4_DPORT, beside xfg_ring_egress with XFG_EGRESS_MULTIBUF on
+    the same records and verdicts; and the same records with XDP_PKT_CONTD
+    cleared (every record its own packet) through xfg_steer_egress and
+    xfg_steer_frags_egress over 8 rings.  Legs timed as c3st's."""
+    import numpy as np
+    import torch
+    import xfgpu as G
+    cm = c3m_workload(args, "c3mst")
+    w, nrec, entries, first = cm.w, cm.nrec, cm.entries, cm.first
+    f, n = w.f, w.n
+    npass = int(np.count_nonzero(cm.hv == 2))     # PASS packets: three TX records each
+    kmax = 64
+    d_tx, d_fill, d_c = f.alloc(16 * entries * kmax), f.alloc(8 * entries), f.alloc(8 * (kmax + 2))
+    # the all-end-of-packet batch: the same records, the option words cleared
+    descs = cm.d_descs.download(np.zeros((entries, 2), np.uint64))
+    descs[:, 1] &= np.uint64(0xffffffff)
+    d_eop = f.alloc(descs.nbytes)
+    d_eop.upload(descs)
+    del descs
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    ring = dict(rx_first=first, rx_mask=entries - 1, fill_first=entries - 555, fill_mask=entries - 1)
+
+    def egress():
+        f.ring_egress(cm.d_descs.ptr, nrec, cm.d_verd.ptr, d_c.ptr, tx_ptr=d_tx.ptr, fill_ptr=d_fill.ptr,
+                      tx_first=entries - 777, tx_mask=entries - 1, flags=G.EGRESS_MULTIBUF, stream=sp, **ring)
+
+    def steer(call, d_rx, k, mode):
+        queues = G.steer_queues([(d_tx.ptr + 16 * entries * q, entries - 777 + q, entries - 1)
+                                 for q in range(k)])
+        return lambda: call(w.d_umem.ptr, d_rx.ptr, nrec, cm.d_verd.ptr, d_c.ptr, queues, mode=mode,
+                            fill_ptr=d_fill.ptr, stream=sp, **ring)
+
+    legs = {"ring_egress_multibuf": egress}
+    for k in (1, 8, 64):
+        legs[f"steer_frags_hash_k{k}"] = steer(f.steer_frags_egress, cm.d_descs, k, G.STEER_L4_HASH)
+        legs[f"steer_frags_dport_k{k}"] = steer(f.steer_frags_egress, cm.d_descs, k, G.STEER_L4_DPORT)
+    legs["all_eop_steer_hash_k8"] = steer(f.steer_egress, d_eop, 8, G.STEER_L4_HASH)
+    legs["all_eop_steer_frags_hash_k8"] = steer(f.steer_frags_egress, d_eop, 8, G.STEER_L4_HASH)
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            call()
+        e0.record(stream)
+        for _ in range(args.iters):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    runs = max(1, args.runs)
+    ms = {k: [] for k in legs}
+    spread = {}
+    for r in range(runs):      # the legs interleaved
+        for k, call in legs.items():
+            ms[k].append(timed(call))
+            if r == 0 and k != "ring_egress_multibuf":
+                nq = int(k.rsplit("k", 1)[1])
+                c = d_c.download(np.zeros(nq + 2, np.uint64)).astype(np.int64)
+                if k.startswith("steer_frags"):
+                    assert int(c[:nq].sum()) == 3 * npass and int(c[nq]) == nrec - 3 * npass, c
+                else:
+                    assert int(c[:nq + 1].sum()) == nrec, c
+                spread[k] = {"min": int(c[:nq].min()), "max": int(c[:nq].max()), "refused": int(c[nq + 1])}
+    # the two calls agree on the all-end-of-packet batch
+    assert spread["all_eop_steer_hash_k8"] == spread["all_eop_steer_frags_hash_k8"], spread
+    # bytes the algorithm moves: a verdict byte and a 16-byte record a record
+    # in, a TX record (16) or a fill address (8) out; steering reads the header
+    # line (64 bytes) of every PASS head, a third of the PASS records here
+    base = 17 * nrec + 16 * 3 * npass + 8 * (nrec - 3 * npass)
+    line = {"config": "c3mst", "program": f.prog_name, "packets": n, "records": nrec,
+            "pass_packets": npass, "ring_entries": entries, "umem_chunk": C3D_CHUNK, "iters": args.iters,
+            "setup_s": round(w.setup_s + time.time() - cm.t0, 1)}
+    ref = min(ms["ring_egress_multibuf"])
+    for k in legs:
+        best = min(ms[k])
+        line[k] = {"ms": [round(m, 4) for m in ms[k]], "vs_ring_egress_multibuf": round(best / ref, 2)}
+        if not k.startswith("all_eop"):
+            moved = base + (0 if k == "ring_egress_multibuf" else 64 * npass)
+            line[k].update(bytes=moved, GBps=round(moved / (best * 1e-3) / 1e9, 1))
+        if k in spread:
+            line[k]["queue_records"] = spread[k]
+    line["all_eop_frags_vs_single"] = round(min(ms["all_eop_steer_frags_hash_k8"]) /
+                                            min(ms["all_eop_steer_hash_k8"]), 3)
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
 def run_c3mc(args):
     """c3m's batch classified by xfg_classify_descs_frags, then its DROP
     packets captured whole (xfg_capture_descs_frags, snaplen 0), head only,
@@ -1187,6 +1286,8 @@ def run(name, args):
         return run_c3m(args)
     if name == "c3mc":
         return run_c3mc(args)
+    if name == "c3mst":
+        return run_c3mst(args)
     if name == "c3mch":
         return run_c3mch(args)
     kind = {"c2": 2, "c3": 3, "c4": 4, "c5": 5, "c3sd": 3, "c3e": 3}[name]

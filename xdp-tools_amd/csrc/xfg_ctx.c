@@ -59,6 +59,7 @@ int xfg_launch_socks_frags_heads(const struct xfg_socks_frags_kargs *a, unsigned
 int xfg_launch_socks_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uint8_t *verdicts,
 				  uint32_t n, unsigned grid, void *stream);
 int xfg_launch_steer(const struct xfg_steer_kargs *a, unsigned grid, void *stream);
+int xfg_launch_steer_frags(const struct xfg_steer_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_frags_egress(const struct xfg_socks_frags_egress_kargs *a, unsigned grid,
 				  void *stream);
 int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
@@ -2788,6 +2789,7 @@ _Static_assert(XFG_STEER_TABLE_BYTES(XFG_STEER_QUEUES, XFG_STEER_AVAIL) <= SOCKS
 
 struct steer_job {
 	const struct xfg_steer *s;
+	int frags;
 	struct xfg_steer_kargs a;
 };
 
@@ -2813,19 +2815,23 @@ static int steer_go(struct xfg_dev *d, unsigned grid, void *arg)
 	a->queues = (const struct xfg_sock_ring *)d->sk_dev[k];
 	a->avail = (const uint8_t *)(a->queues + a->nqueues);
 	a->state = d->cstatus;
-	err = xfg_launch_steer(a, grid, d->stream);
+	err = j->frags ? xfg_launch_steer_frags(a, grid, d->stream) : xfg_launch_steer(a, grid, d->stream);
 	return socks_table_done(d, k, err);
 fail:
 	return err;
 }
 
-int xfg_steer_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s, const uint8_t *verdicts,
-		     void *stream)
+/* Both steer calls: the single-buffer one, and with @frags the multi-buffer
+ * one (the same structure, checks and table; XFG_EGRESS_MULTIBUF is then a flag
+ * it takes, and the state has the column of the records that are not live). */
+static int steer_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s, const uint8_t *verdicts,
+			void *stream, int frags)
 {
+	const uint32_t flags_ok = XFG_EGRESS_SWAP_MACS | (frags ? XFG_EGRESS_MULTIBUF : 0);
 	int err;
 	if (!ctx || !s || s->sz < sizeof(*s) || !s->queues || !s->nqueues ||
 	    s->nqueues > XFG_STEER_QUEUES_MAX || s->skip_queue >= s->nqueues ||
-	    s->mode > XFG_STEER_L4_DPORT || (s->flags & ~XFG_EGRESS_SWAP_MACS) ||
+	    s->mode > XFG_STEER_L4_DPORT || (s->flags & ~flags_ok) ||
 	    s->count > 0xffffffffull || !s->counts)
 		return -EINVAL;
 	const uint32_t navail = s->avail ? s->navail : s->nqueues;
@@ -2853,7 +2859,7 @@ int xfg_steer_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s, const uin
 	if ((err = dev_check(ctx, dev)))
 		return err;
 	struct steer_job j = {
-		.s = s,
+		.s = s, .frags = frags,
 		.a = {
 			.umem = s->umem, .rx = s->rx_descs, .fill = s->fill_addrs, .verdicts = verdicts,
 			.queue_of = s->queue_of, .counts = (unsigned long long *)s->counts,
@@ -2865,8 +2871,22 @@ int xfg_steer_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s, const uin
 		},
 	};
 	return scratch_launch(&ctx->dev[dev], stream, s->count ? NULL : s->counts,
-			      ((size_t)s->nqueues + 2) * 8, XFG_STEER_STATE_WORDS(s->count, s->nqueues),
+			      ((size_t)s->nqueues + 2) * 8,
+			      frags ? XFG_STEER_FRAGS_STATE_WORDS(s->count, s->nqueues)
+				    : XFG_STEER_STATE_WORDS(s->count, s->nqueues),
 			      steer_go, &j);
+}
+
+int xfg_steer_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s, const uint8_t *verdicts,
+		     void *stream)
+{
+	return steer_egress(ctx, dev, s, verdicts, stream, 0);
+}
+
+int xfg_steer_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s, const uint8_t *verdicts,
+			   void *stream)
+{
+	return steer_egress(ctx, dev, s, verdicts, stream, 1);
 }
 
 /* Multi-buffer batches of many sockets (include/xdpfilter_gpu.h), a staged

@@ -2224,5 +2224,6 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // steered egress (PASS frames over K workers' TX rings by flow): the egress
 // kernel's scheme with K sums a tile and a wave-wide look-back
 #include "xfg_steer.hip"
+#include "xfg_steer_frags.hip"
 
 #endif   // XFG_PART_COMMON

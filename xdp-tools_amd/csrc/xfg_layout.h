@@ -598,6 +598,13 @@ struct xfg_steer_kargs {
 #define XFG_STEER_STATUS(t, nqueues) (2 + (uint64_t)(t) * (nqueues))
 /* (an even count: the launch's one memset is then a multiple of 16 bytes) */
 #define XFG_STEER_STATE_WORDS(n, nqueues) ((XFG_STEER_STATUS(XFG_STEER_TILES(n), nqueues) + 1) & ~1ull)
+/* Steered egress of multi-buffer packets (xfg_steer_frags.hip,
+ * xfg_steer_frags_egress()): the same arguments, table and K columns, and
+ * behind the columns one more status word a tile -- the running count of the
+ * records that are not live, which the fill positions need. */
+#define XFG_STEER_FRAGS_DEAD(n, nqueues) XFG_STEER_STATUS(XFG_STEER_TILES(n), nqueues)
+#define XFG_STEER_FRAGS_STATE_WORDS(n, nqueues) \
+	((XFG_STEER_FRAGS_DEAD(n, nqueues) + XFG_STEER_TILES(n) + 1) & ~1ull)
 #define XFG_STEER_TABLE_BYTES(nqueues, navail) \
 	((uint64_t)(nqueues) * sizeof(struct xfg_sock_ring) + (uint64_t)(navail))
 

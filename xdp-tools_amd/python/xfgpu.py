@@ -67,7 +67,7 @@ EXPORTS = [
     "xfg_classify_socks_frags", "xfg_socks_frags_egress", "xfg_capture_descs_frags",
     "xfg_classify_chain", "xfg_classify_descs_chain", "xfg_classify_descs_chain_timed",
     "xfg_classify_descs_frags_chain", "xfg_classify_descs_frags_chain_timed",
-    "xfg_steer_egress",
+    "xfg_steer_egress", "xfg_steer_frags_egress",
 ]
 CAPTURE_HEAD_ONLY = 1        # XFG_CAPTURE_HEAD_ONLY
 SOCKS_MAX = 1024
@@ -292,6 +292,7 @@ def _load():
         "xfg_ring_egress": (C.c_int, [vp, C.c_int, C.POINTER(Egress), vp, vp]),
         "xfg_classify_socks": (C.c_int, [vp, C.c_int, C.POINTER(Socks), vp, vp]),
         "xfg_steer_egress": (C.c_int, [vp, C.c_int, C.POINTER(Steer), vp, vp]),
+        "xfg_steer_frags_egress": (C.c_int, [vp, C.c_int, C.POINTER(Steer), vp, vp]),
         "xfg_socks_egress": (C.c_int, [vp, C.c_int, C.POINTER(Socks), C.POINTER(SocksEgress), vp,
                                        vp]),
         "xfg_classify_socks_frags": (C.c_int, [vp, C.c_int, C.POINTER(Socks),
@@ -774,6 +775,24 @@ class Filter:
                   queue_of_ptr, flags)
         _check(lib.xfg_steer_egress(self.ctx, dev, C.byref(s), verdicts_ptr, stream),
                "steer_egress")
+
+    def steer_frags_egress(self, umem_ptr, rx_ptr, count, verdicts_ptr, counts_ptr, queues,
+                           avail=None, mode=STEER_L4_HASH, skip_queue=0, nqueues=None,
+                           fill_ptr=None, rx_first=0, rx_mask=0xffffffff, fill_first=0,
+                           fill_mask=0xffffffff, queue_of_ptr=None, flags=0, dev=0, stream=None):
+        """The same over multi-buffer packets (xfg_steer_frags_egress): every
+        live record of a packet whose head is PASS to the TX ring of the head
+        frame's queue, every live record of any other packet to the fill ring;
+        a record whose verdict byte is VERDICT_NONE to neither.  Arguments as
+        for steer_egress; flags may carry EGRESS_MULTIBUF."""
+        tab = queues if isinstance(queues, C.Array) else steer_queues(queues)
+        av = None if avail is None else (C.c_uint32 * max(len(avail), 1))(*[int(a) for a in avail])
+        s = Steer(C.sizeof(Steer), umem_ptr, rx_ptr, rx_first, rx_mask, tab, av,
+                  len(queues) if nqueues is None else nqueues, 0 if avail is None else len(avail),
+                  mode, skip_queue, fill_ptr, fill_first, fill_mask, count, counts_ptr,
+                  queue_of_ptr, flags)
+        _check(lib.xfg_steer_frags_egress(self.ctx, dev, C.byref(s), verdicts_ptr, stream),
+               "steer_frags_egress")
 
     def classify_socks(self, umem_ptr, socks, verdicts_ptr, nsocks=None, flat_ptr=None, dev=0,
                        stream=None):
