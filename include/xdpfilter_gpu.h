@@ -777,6 +777,185 @@ int xfg_steer_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s,
 			   const uint8_t *verdicts, void *stream);
 
 /*
+ * A forwarding table (FIB) for xfg_forward_egress below: IPv4 routes with
+ * longest-prefix match, and the next hops they name -- what bpf_fib_lookup
+ * answers xdp-forward (xdp-forward/xdp_forward.bpf.c:87) from the kernel's
+ * route and neighbour tables, as data the caller supplies.
+ *
+ * A route is (prefix, len, nexthop): prefix in host order (10.0.0.0/8 is
+ * 0x0a000000, len 8), no bit set below len; len 0 is the default route;
+ * nexthop an index into the next-hop array.  A next hop is what the lookup
+ * leaves in fib_params for it: the egress ifindex (never 0), the route's mtu
+ * (0: not checked), the two MAC addresses, and ret -- 0 for
+ * BPF_FIB_LKUP_RET_SUCCESS, else the non-zero return the lookup gives for this
+ * next hop (blackhole, unreachable, prohibit, no neighbour, ...).
+ *
+ * The table is DIR-24-8 with 16-bit entries: a first table of 2^24 entries
+ * (32 MiB) indexed by the address's top 24 bits, 256-entry second-level groups
+ * for the /24s that hold a prefix longer than /24, and a dense array of
+ * 32-byte next-hop records.  An entry is 0 (no route), next hop + 1, or
+ * 0x8000 | group in the first table.  So an address covered by nothing longer
+ * than /24 costs one table load, every other two, and "no route" is an entry
+ * value.  That format holds XFG_FIB_NEXTHOPS_MAX next hops and
+ * XFG_FIB_GROUPS_MAX groups.
+ *
+ * A FIB is immutable: to change a route, build a new one and pass that to the
+ * next call (the old one may be freed once the calls that use it have
+ * completed on the device).  The builder keeps a host copy of the tables,
+ * which xfg_fib_lookup_host reads; on a host-only context xfg_fib_create
+ * builds just that copy (dev is then not looked at), on a device context it
+ * also uploads the tables to device @dev once, before it returns.  The arrays
+ * passed in are not kept.  IPv6 routes, policy routing (the lookup's tos,
+ * l4_protocol, source address and ingress ifindex inputs) and in-place updates
+ * are not modelled.
+ *
+ * xfg_fib_create -- -EINVAL: ctx or out NULL, routes NULL with nroutes != 0,
+ * nexthops NULL with nnexthops != 0, dev out of range on a device context, a
+ * route with len > 32, with prefix bits set below len or with nexthop >=
+ * nnexthops, a next hop with ifindex 0.  -ENOSPC: more than
+ * XFG_FIB_NEXTHOPS_MAX next hops, or more than XFG_FIB_GROUPS_MAX /24s with a
+ * longer prefix in them.  -EEXIST: the same (prefix, len) given twice.
+ * -ENOMEM.  xfg_fib_lookup_host: the longest match's next hop in *nexthop and
+ * 0; -ENOENT: no route covers @dst (host order); -EINVAL: fib NULL.
+ */
+#define XFG_FIB_NEXTHOPS_MAX 32767u
+#define XFG_FIB_GROUPS_MAX   32768u
+
+typedef struct xfg_fib xfg_fib;
+
+struct xfg_fib_nexthop {
+	uint32_t ifindex;           /* egress port, as fib_params.ifindex comes back; != 0 */
+	uint16_t mtu;               /* 0: not checked */
+	uint8_t  ret;               /* 0: BPF_FIB_LKUP_RET_SUCCESS; else the lookup's return */
+	uint8_t  dmac[6], smac[6];
+};
+
+struct xfg_fib_route {
+	uint32_t prefix;            /* host order */
+	uint32_t nexthop;
+	uint8_t  len;
+};
+
+int xfg_fib_create(xfg_ctx *ctx, int dev, const struct xfg_fib_route *routes, uint64_t nroutes,
+		   const struct xfg_fib_nexthop *nexthops, uint32_t nnexthops, xfg_fib **out);
+void xfg_fib_free(xfg_fib *fib);
+int xfg_fib_lookup_host(const xfg_fib *fib, uint32_t dst, uint32_t *nexthop);
+
+/*
+ * Forwarded egress: where a passed frame goes, decided on the device by a FIB
+ * -- "filter, then route".  This is xdp-forward's xdp_fwd_fib_full
+ * (xdp-forward/xdp_forward.bpf.c:32-133) with a TX ring in the place of an
+ * xdp_tx_ports entry and an xfg_fib in the place of bpf_fib_lookup.
+ *
+ * Records, verdicts, the fill side, the entry formats, masks, index wrap, ring
+ * overlap and stream ordering are xfg_steer_egress's: record i is
+ * rx_descs[(rx_first + i) & rx_mask] with verdict byte verdicts[i]; a record
+ * whose verdict is not XFG_XDP_PASS hands its chunk to the fill ring.  A PASS
+ * record's frame, bytes [0, len) in the UMEM, goes through the program:
+ * parse_ethhdr (headers/xdp/parsing_helpers.h:100-134, VLAN_MAX_DEPTH 4), then
+ * parse_iphdr (:201-233), the TTL check, the lookup, the xdp_tx_ports check.
+ * It gets one reason, the first of these rows that holds:
+ *
+ *   XFG_FWD_NOT_IP   len < 14, or after up to four 802.1Q/802.1AD tags the
+ *                    ethertype is neither IPv4 nor IPv6.  A tag that does not
+ *                    fit in the frame ends the loop and leaves the VLAN
+ *                    ethertype (:123-124), and so does a fifth tag
+ *                    (xdp_forward.bpf.c:45-46,81-83).
+ *   XFG_FWD_BAD_HDR  IPv4 and l3 + 20 > len or l3 + 4 * ihl > len, l3 the
+ *                    offset behind the tags.  The program has no ihl >= 5
+ *                    check, so there is none here (:47-49).
+ *   XFG_FWD_TTL      ttl <= 1 (:51-52).
+ *   XFG_FWD_V6       the ethertype is IPv6: this FIB has no IPv6 table, and
+ *                    every path of the program through a failed lookup returns
+ *                    XDP_PASS.  The frame is not parsed further (:62-80,126).
+ *   XFG_FWD_NO_ROUTE no prefix covers daddr (:126).
+ *   XFG_FWD_NH_RET   the next hop's ret != 0 (:126).
+ *   XFG_FWD_FRAG     the next hop's mtu != 0 and ntohs(tot_len) > mtu -- the
+ *                    header field, not the record's len (:59,126).
+ *   XFG_FWD_NO_PORT  the next hop's ifindex is not among ports (:113-114).
+ *   XFG_FWD_OK       forwarded (:104-123).
+ *
+ * (The program returns XDP_PASS for NO_ROUTE .. NO_PORT alike; their order is
+ * this library's own.)  XFG_FWD_OK sends the record to TX ring q, the index of
+ * the next hop's ifindex in ports, and rewrites the frame in the UMEM as
+ * :116-122 do: ip_decrease_ttl (:23-30) literally -- the check field loaded as
+ * the little-endian 16-bit value of its bytes, plus htons(0x0100), plus 1 if
+ * that sum is >= 0xFFFF, truncated to 16 bits; ttl - 1 -- then bytes 0..5 =
+ * dmac, bytes 6..11 = smac.  The VLAN tags and every other byte of the UMEM
+ * keep their values.  Every other PASS frame goes to the stack ring untouched:
+ * the ring of the frames the program returns XDP_PASS for.  The descriptors of
+ * one batch must name distinct frames.
+ *
+ * Order within every ring is batch order.  queue_of[i] (when given): q, or
+ * nports for the stack ring, or XFG_QUEUE_NONE for a record that is not PASS.
+ * reason_of[i] (when given): the reason of a PASS record, XFG_QUEUE_NONE for
+ * any other.  counts (device, (nports + 2 + XFG_FWD_REASONS) x u64): counts[q]
+ * the TX records of port q, counts[nports] the stack records, counts[nports +
+ * 1] the fill-side records (whether their fill entries were written or not),
+ * counts[nports + 2 + r] the PASS frames with reason r.  count == 0: the
+ * counts are zeroed and nothing else is written.
+ *
+ * xdp_tx_ports holds 64 entries; this call takes XFG_FWD_PORTS_MAX = 63: the
+ * stack ring is the 64th queue of the 64-lane look-back.  ports is HOST memory
+ * and may be reused as soon as the call returns: it reaches the device through
+ * the pinned staging slots of the socket calls, so the call makes no host
+ * synchronisation.  Every port's ring, the stack ring and the fill ring need at
+ * least count entries.  The UMEM is read for every PASS frame -- the first 64
+ * bytes that lie below len rounded up to 16 (frame starts are 16-byte aligned)
+ * -- and written for every forwarded one, within those bytes.
+ *
+ * Limits: IPv4 only (an IPv6 frame goes to the stack ring with XFG_FWD_V6); 63
+ * ports; an immutable FIB; single-buffer frames (a multi-buffer batch must not
+ * be passed: a continuation record would be parsed as a frame).  Many-socket
+ * rounds run over the flat array xfg_classify_socks leaves.  Not covered: the
+ * host-memory path, the CLI, the xdp_flowtable programs.
+ *
+ * -EINVAL: everything xfg_steer_egress refuses of the fields the two share,
+ * and: fib NULL, of another context or built for another device; nports 0 or
+ * above XFG_FWD_PORTS_MAX; ports NULL; a port without a ring, with ifindex 0
+ * or with an ifindex given twice; stack.tx_descs NULL; any flag.  -ENODEV on a
+ * host-only context, after these checks; no device pointer is dereferenced
+ * before it.
+ */
+#define XFG_FWD_PORTS_MAX 63u
+#define XFG_FWD_OK        0u
+#define XFG_FWD_NOT_IP    1u
+#define XFG_FWD_BAD_HDR   2u
+#define XFG_FWD_TTL       3u
+#define XFG_FWD_V6        4u
+#define XFG_FWD_NO_ROUTE  5u
+#define XFG_FWD_NH_RET    6u
+#define XFG_FWD_FRAG      7u
+#define XFG_FWD_NO_PORT   8u
+#define XFG_FWD_REASONS   9u
+
+struct xfg_fwd_port {           /* one egress port: an xdp_tx_ports entry and its TX ring */
+	uint32_t ifindex;
+	void *tx_descs;
+	uint32_t tx_first, tx_mask;
+};
+
+struct xfg_forward {
+	size_t sz;                  /* sizeof(struct xfg_forward), for extension */
+	void *umem;                 /* device; read for every PASS frame, written for every forwarded one */
+	const void *rx_descs;
+	uint32_t rx_first, rx_mask;
+	const xfg_fib *fib;
+	const struct xfg_fwd_port *ports;   /* HOST, nports entries: the program's xdp_tx_ports */
+	uint32_t nports;
+	struct xfg_steer_queue stack;       /* the ring of the frames the program returns XDP_PASS for */
+	uint64_t *fill_addrs;       /* NULL: no fill entries written */
+	uint32_t fill_first, fill_mask;
+	uint64_t count;             /* < 2^32 */
+	uint64_t *counts;           /* device, (nports + 2 + XFG_FWD_REASONS) x u64 */
+	uint8_t *queue_of, *reason_of;      /* device, count bytes each, or NULL */
+	uint32_t flags;             /* none defined: non-zero is refused */
+};
+
+int xfg_forward_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f,
+		       const uint8_t *verdicts, void *stream);
+
+/*
  * Many sockets over one UMEM: one classify and one egress for a whole poll
  * round.  An AF_XDP application has one socket per NIC queue over a shared
  * UMEM (lib/util/xdpsock.c:1788-1809) and peeks a small batch (batch_size 64,

@@ -31,6 +31,14 @@
       frames over 1, 8 and 64 workers' TX rings in modes L4_HASH and L4_DPORT,
       beside xfg_ring_egress on the same batch and verdicts, timed as c3f's
       legs are; the records a queue gets (least, most) and the refused frames
+  c3fw c3d's batch classified, then forwarded over 8 ports (xfg_forward_egress)
+      by a FIB of 2^20 synthetic routes (80% /24, 20% /25../32, over a default
+      route) and again by a FIB of the default route alone -- the difference is
+      what the table costs -- beside xfg_steer_egress at K = 8 (L4_HASH) and
+      xfg_ring_egress with the MAC swap on the same verdicts, timed as c3f's
+      legs are; the PASS frames by reason after the first call, and the
+      forwarded frames after every run (every call decrements their TTL: a run
+      after which fewer frames are forwarded is left out of the figures)
   c3c  c3d's batch classified, then its DROP frames captured as pcapng blocks
       (xfg_capture_descs, snaplen 0), beside xfg_compact; the same ring with
       1514-byte frames at snaplen 96, one in ten selected; one tile of
@@ -407,6 +415,114 @@ def run_c3st(args):
                    "GBps": round(moved / (best * 1e-3) / 1e9, 1), "vs_ring_egress": round(best / ref, 2)}
         if k in spread:
             line[k]["queue_records"] = spread[k]
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
+def c3fw_fib(f, G, nroutes, nports):
+    """A FIB of a default route and up to nroutes - 1 distinct random routes,
+    80% of them /24 and 20% /25../32, over 4 next hops a port.  The longer ones
+    lie in 2^14 /24s: the entry format holds 2^15 second-level groups."""
+    import numpy as np
+    rng = np.random.default_rng(20)
+    nnh = 4 * nports
+    length = np.where(rng.random(nroutes) < 0.8, 24, rng.integers(25, 33, nroutes))
+    prefix = rng.integers(0, 1 << 32, nroutes)
+    homes = rng.integers(0, 1 << 24, 1 << 14) << 8
+    prefix = np.where(length > 24, homes[rng.integers(0, len(homes), nroutes)] | (prefix & 0xff), prefix)
+    prefix &= (0xffffffff << (32 - length)) & 0xffffffff
+    key = np.unique((prefix << 6) | length)[:max(nroutes - 1, 0)]
+    routes = np.empty((len(key) + 1, 3), np.int64)
+    routes[0] = (0, 0, 0)
+    routes[1:, 0], routes[1:, 1] = key >> 6, key & 63
+    routes[1:, 2] = rng.integers(0, nnh, len(key))
+    nexthops = [(10 + k % nports, 0, 0, bytes([2, 1, 0, 0, 0, k]), bytes([2, 2, 0, 0, 0, k]))
+                for k in range(nnh)]
+    return G.Fib(f, routes, nexthops), len(routes)
+
+
+def run_c3fw(args):
+    """c3d's batch classified, then forwarded over 8 ports by a large FIB and
+    by a default route alone, beside the steer call at K = 8 and the ring
+    egress with the MAC swap.  Legs timed as c3f's."""
+    import numpy as np
+    import torch
+    import xfgpu as G
+    w = c3d_workload(args, "c3fw")
+    f, n, entries, first = w.f, w.n, w.entries, w.first
+    f.classify_descs(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, first=first, mask=entries - 1)
+    f.sync()
+    npass = int(np.count_nonzero(w.d_verd.download(np.zeros(n, np.uint8)) == 2))
+    P = 8
+    ncounts = P + 2 + G.FWD_REASONS
+    d_tx, d_fill, d_c = f.alloc(16 * n * (P + 1)), f.alloc(8 * n), f.alloc(8 * ncounts)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    rings = [(d_tx.ptr + 16 * n * q, n - 777 + q, n - 1) for q in range(P + 1)]
+    ports = G.fwd_ports([(10 + q,) + rings[q] for q in range(P)])
+    queues = G.steer_queues(rings[:P])
+    fibs = {"forward_2p20": c3fw_fib(f, G, 1 << 20, P), "forward_default": c3fw_fib(f, G, 1, P)}
+
+    def forward(fib):
+        return lambda: f.forward_egress(w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, d_c.ptr, fib, ports,
+                                        rings[P], fill_ptr=d_fill.ptr, rx_first=first,
+                                        rx_mask=entries - 1, fill_first=n - 555, fill_mask=n - 1, stream=sp)
+
+    legs = {k: forward(fib) for k, (fib, _) in fibs.items()}
+    legs["steer_hash_k8"] = lambda: f.steer_egress(
+        w.d_umem.ptr, w.d_descs.ptr, n, w.d_verd.ptr, d_c.ptr, queues, mode=G.STEER_L4_HASH,
+        fill_ptr=d_fill.ptr, rx_first=first, rx_mask=entries - 1, fill_first=n - 555, fill_mask=n - 1,
+        stream=sp)
+    legs["ring_egress_swap"] = lambda: f.ring_egress(
+        w.d_descs.ptr, n, w.d_verd.ptr, d_c.ptr, tx_ptr=d_tx.ptr, fill_ptr=d_fill.ptr, rx_first=first,
+        rx_mask=entries - 1, tx_first=n - 777, tx_mask=n - 1, fill_first=n - 555, fill_mask=n - 1,
+        umem_ptr=w.d_umem.ptr, flags=G.EGRESS_SWAP_MACS, stream=sp)
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            call()
+        e0.record(stream)
+        for _ in range(args.iters):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    def reasons():
+        c = d_c.download(np.zeros(ncounts, np.uint64)).astype(np.int64)
+        assert int(c[:P + 1].sum()) == npass and int(c[P + 1]) == n - npass, c
+        return {"ports": c[:P].tolist(), "stack": int(c[P]), "reasons": c[P + 2:].tolist()}
+
+    runs = max(1, args.runs)
+    ms = {k: [] for k in legs}
+    seen = {}
+    for r in range(runs):      # the legs interleaved
+        for k, call in legs.items():
+            if r == 0 and k in fibs:
+                call()
+                torch.cuda.synchronize()
+                seen[k] = {"first_call": reasons()}
+            t = timed(call)
+            if k in fibs:
+                # every call decrements the forwarded frames' TTL: a run counts
+                # only while the frames forwarded are the first call's
+                last = reasons()
+                seen[k].setdefault("forwarded_after_run", []).append(last["reasons"][0])
+                if last != seen[k]["first_call"]:
+                    continue
+            ms[k].append(t)
+    line = {"config": "c3fw", "program": f.prog_name, "packets": n, "pass_frames": npass, "ports": P,
+            "ring_entries": entries, "umem_chunk": C3D_CHUNK, "iters": args.iters,
+            "routes": {k: nr for k, (_, nr) in fibs.items()}, "setup_s": round(w.setup_s, 1)}
+    ref = min(ms["steer_hash_k8"])
+    for k in legs:
+        best = min(ms[k])
+        line[k] = {"ms": [round(m, 4) for m in ms[k]], "vs_steer_hash_k8": round(best / ref, 2)}
+        line[k].update(seen.get(k, {}))
+    line["table_cost_ms"] = round(min(ms["forward_2p20"]) - min(ms["forward_default"]), 4)
+    for fib, _ in fibs.values():
+        fib.free()
     f.close()
     print(json.dumps(line), flush=True)
 
@@ -1282,6 +1398,8 @@ def run(name, args):
         return run_c3f(args)
     if name == "c3st":
         return run_c3st(args)
+    if name == "c3fw":
+        return run_c3fw(args)
     if name == "c3m":
         return run_c3m(args)
     if name == "c3mc":

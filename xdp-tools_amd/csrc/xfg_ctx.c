@@ -28,6 +28,7 @@
 #include "xfg_layout.h"
 #include "xfg_plan.h"
 #include "xfg_table.h"
+#include "xfg_fib.h"
 
 /* from xfg_kernels.hip */
 int xfg_launch_log_count(const struct xfg_kargs *a, void *stream);
@@ -60,6 +61,7 @@ int xfg_launch_socks_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uin
 				  uint32_t n, unsigned grid, void *stream);
 int xfg_launch_steer(const struct xfg_steer_kargs *a, unsigned grid, void *stream);
 int xfg_launch_steer_frags(const struct xfg_steer_kargs *a, unsigned grid, void *stream);
+int xfg_launch_forward(const struct xfg_fwd_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_frags_egress(const struct xfg_socks_frags_egress_kargs *a, unsigned grid,
 				  void *stream);
 int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
@@ -2887,6 +2889,150 @@ int xfg_steer_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_steer *s, con
 			   void *stream)
 {
 	return steer_egress(ctx, dev, s, verdicts, stream, 1);
+}
+
+/* The forwarding table (include/xdpfilter_gpu.h): xfg_fib.c builds the host
+ * copy; on a device context its three arrays are uploaded here, once. */
+int xfg_fib_create(xfg_ctx *ctx, int dev, const struct xfg_fib_route *routes, uint64_t nroutes,
+		   const struct xfg_fib_nexthop *nexthops, uint32_t nnexthops, xfg_fib **out)
+{
+	xfg_fib *f = NULL;
+	int err;
+	if (!ctx || !out || (ctx->ndev && (dev < 0 || dev >= ctx->ndev)))
+		return -EINVAL;
+	if ((err = xfg_fib_build_host(routes, nroutes, nexthops, nnexthops, &f)))
+		return err;
+	f->ctx = ctx;
+	if (ctx->ndev) {
+		const struct { void **d; const void *h; size_t bytes; } up[3] = {
+			{ &f->d_t24, f->t24, (size_t)XFG_FIB_T24_ENTRIES * 2 },
+			{ &f->d_t8, f->t8, (size_t)(f->ngroups ? f->ngroups : 1) * XFG_FIB_GROUP * 2 },
+			{ &f->d_nh, f->nh, (size_t)(f->nnh ? f->nnh : 1) * sizeof(*f->nh) },
+		};
+		f->dev = dev;
+		for (int i = 0; i < 3 && !err; i++) {
+			if (!(*up[i].d = xfg_dev_alloc(ctx, dev, up[i].bytes)))
+				err = -ENOMEM;
+			else
+				err = xfg_memcpy_h2d(ctx, dev, *up[i].d, up[i].h, up[i].bytes);
+		}
+		if (err) {
+			xfg_fib_free(f);
+			return err;
+		}
+	}
+	*out = f;
+	return 0;
+}
+
+void xfg_fib_free(xfg_fib *f)
+{
+	if (!f)
+		return;
+	if (f->dev >= 0) {
+		xfg_dev_free(f->ctx, f->dev, f->d_t24);
+		xfg_dev_free(f->ctx, f->dev, f->d_t8);
+		xfg_dev_free(f->ctx, f->dev, f->d_nh);
+	}
+	xfg_fib_free_host(f);
+}
+
+/* Forwarded egress (include/xdpfilter_gpu.h): the ports' rings, the stack
+ * ring and the ifindex -> queue hash reach the device as the steer call's
+ * table does, through the next staging slot. */
+_Static_assert(XFG_FWD_PORTS_MAX + 1 == XFG_STEER_QUEUES && XFG_FWD_REASONS == XFG_FWD_NREASONS,
+	       "the kernel's tables");
+_Static_assert(XFG_FWD_TABLE_BYTES(XFG_STEER_QUEUES) <= SOCKS_SLOT_BYTES, "a staging slot holds the table");
+_Static_assert(2 * XFG_FWD_PORTS_MAX <= XFG_FWD_HASH_SLOTS, "a probe meets an empty slot");
+
+struct forward_job {
+	const struct xfg_forward *f;
+	struct xfg_fwd_kargs a;
+};
+
+static int forward_go(struct xfg_dev *d, unsigned grid, void *arg)
+{
+	struct forward_job *j = arg;
+	const struct xfg_forward *f = j->f;
+	struct xfg_fwd_kargs *a = &j->a;
+	const int k = (int)d->sk_next;
+	int err = socks_slot(d, k);
+	if (err)
+		return err;
+	struct xfg_sock_ring *hq = (struct xfg_sock_ring *)d->sk_host[k];
+	struct xfg_fwd_slot *hs = (struct xfg_fwd_slot *)(hq + a->nqueues);
+	memset(hs, 0, XFG_FWD_HASH_SLOTS * sizeof(*hs));
+	for (uint32_t q = 0; q < f->nports; q++) {
+		const struct xfg_fwd_port *p = &f->ports[q];
+		hq[q] = (struct xfg_sock_ring){ (uintptr_t)p->tx_descs, p->tx_first, p->tx_mask };
+		uint32_t s = xfg_fwd_hash(p->ifindex);
+		while (hs[s].ifindex)
+			s = (s + 1) % XFG_FWD_HASH_SLOTS;
+		hs[s] = (struct xfg_fwd_slot){ p->ifindex, q };
+	}
+	hq[f->nports] = (struct xfg_sock_ring){ (uintptr_t)f->stack.tx_descs, f->stack.tx_first,
+						f->stack.tx_mask };
+	HIPCHK(hipMemcpyAsync(d->sk_dev[k], d->sk_host[k], XFG_FWD_TABLE_BYTES(a->nqueues),
+			      hipMemcpyHostToDevice, d->stream));
+	d->sk_next = (uint32_t)(k + 1) % SOCKS_SLOTS;
+	a->queues = (const struct xfg_sock_ring *)d->sk_dev[k];
+	a->hash = (const struct xfg_fwd_slot *)(a->queues + a->nqueues);
+	a->state = d->cstatus;
+	err = xfg_launch_forward(a, grid, d->stream);
+	return socks_table_done(d, k, err);
+fail:
+	return err;
+}
+
+int xfg_forward_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f, const uint8_t *verdicts,
+		       void *stream)
+{
+	int err;
+	if (!ctx || !f || f->sz < sizeof(*f) || !f->fib || f->fib->ctx != ctx || !f->ports ||
+	    !f->nports || f->nports > XFG_FWD_PORTS_MAX || f->flags || f->count > 0xffffffffull ||
+	    !f->counts)
+		return -EINVAL;
+	if (ctx->ndev && f->fib->dev != dev)
+		return -EINVAL;
+	if (!mask_ok(f->rx_mask) || (f->fill_addrs && !mask_ok(f->fill_mask)))
+		return -EINVAL;
+	if (((uintptr_t)f->umem & 7) || ((uintptr_t)f->rx_descs & 7) || ((uintptr_t)f->fill_addrs & 7) ||
+	    ((uintptr_t)f->counts & 7))
+		return -EINVAL;
+	if (f->fill_addrs && (uint64_t)f->fill_mask + 1 < f->count)
+		return -EINVAL;
+	for (uint32_t q = 0; q <= f->nports; q++) {
+		const void *tx = q < f->nports ? f->ports[q].tx_descs : f->stack.tx_descs;
+		const uint32_t mask = q < f->nports ? f->ports[q].tx_mask : f->stack.tx_mask;
+		if (!tx || ((uintptr_t)tx & 7) || !mask_ok(mask) || (uint64_t)mask + 1 < f->count)
+			return -EINVAL;
+		if (q == f->nports)
+			break;
+		if (!f->ports[q].ifindex)
+			return -EINVAL;
+		for (uint32_t p = 0; p < q; p++)
+			if (f->ports[p].ifindex == f->ports[q].ifindex)
+				return -EINVAL;
+	}
+	if (f->count && (!f->umem || !f->rx_descs || !verdicts))
+		return -EINVAL;
+	if ((err = dev_check(ctx, dev)))
+		return err;
+	struct forward_job j = {
+		.f = f,
+		.a = {
+			.umem = f->umem, .rx = f->rx_descs, .t24 = f->fib->d_t24, .t8 = f->fib->d_t8,
+			.nh = f->fib->d_nh, .fill = f->fill_addrs, .verdicts = verdicts,
+			.queue_of = f->queue_of, .reason_of = f->reason_of,
+			.counts = (unsigned long long *)f->counts,
+			.rx_first = f->rx_first, .rx_mask = f->rx_mask,
+			.fill_first = f->fill_first, .fill_mask = f->fill_mask,
+			.n = (uint32_t)f->count, .nqueues = f->nports + 1,
+		},
+	};
+	return scratch_launch(&ctx->dev[dev], stream, f->count ? NULL : f->counts,
+			      ((size_t)f->nports + 2 + XFG_FWD_REASONS) * 8,
+			      XFG_STEER_STATE_WORDS(f->count, f->nports + 1), forward_go, &j);
 }
 
 /* Multi-buffer batches of many sockets (include/xdpfilter_gpu.h), a staged

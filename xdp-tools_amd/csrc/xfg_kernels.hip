@@ -2226,4 +2226,9 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 #include "xfg_steer.hip"
 #include "xfg_steer_frags.hip"
 
+// forwarded egress (PASS frames to the egress port a FIB lookup names, the
+// header rewritten): the steer partition with another choice of queue
+#include "xfg_fib.h"
+#include "xfg_forward.hip"
+
 #endif   // XFG_PART_COMMON

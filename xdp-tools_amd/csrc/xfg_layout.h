@@ -608,6 +608,42 @@ struct xfg_steer_kargs {
 #define XFG_STEER_TABLE_BYTES(nqueues, navail) \
 	((uint64_t)(nqueues) * sizeof(struct xfg_sock_ring) + (uint64_t)(navail))
 
+/* Forwarded egress (xfg_forward.hip, xfg_forward_egress()): the steer
+ * partition with the queue chosen by a FIB lookup (xfg_fib.h) and the header
+ * rewritten.  Queue q < nports is port q's TX ring, queue nports the stack
+ * ring: nqueues = nports + 1.  A launch's table in a staging slot is the
+ * nqueues rings, one struct xfg_sock_ring each, and behind them the ports'
+ * ifindex -> queue map: an open-addressing hash of XFG_FWD_HASH_SLOTS {ifindex,
+ * queue} pairs, built by the host (slot xfg_fwd_hash(ifindex), linear probing,
+ * ifindex 0: empty -- at most 63 of the slots are taken, so a probe ends).
+ * The state words are XFG_STEER_STATE_WORDS(n, nqueues); counts is nports + 2
+ * + XFG_FWD_NREASONS words, of which the launch function zeroes the reasons'
+ * (the tiles add to them). */
+struct xfg_fwd_slot {
+	uint32_t ifindex, queue;
+};
+struct xfg_fwd_kargs {
+	uint8_t *umem;                  /* read for every PASS frame, written for a forwarded one */
+	const void *rx;
+	const struct xfg_sock_ring *queues;   /* the table */
+	const struct xfg_fwd_slot *hash;      /* behind it */
+	const uint16_t *t24, *t8;       /* the FIB (xfg_fib.h) */
+	const void *nh;
+	uint64_t *fill;                 /* NULL: none written */
+	const uint8_t *verdicts;
+	uint8_t *queue_of, *reason_of;  /* NULL: not written */
+	unsigned long long *counts;
+	unsigned long long *state;
+	uint32_t rx_first, rx_mask;
+	uint32_t fill_first, fill_mask;
+	uint32_t n;                     /* records, >= 1 */
+	uint32_t nqueues;               /* nports + 1 */
+};
+#define XFG_FWD_NREASONS 9u         /* XFG_FWD_REASONS */
+#define XFG_FWD_HASH_SLOTS 128u
+#define XFG_FWD_TABLE_BYTES(nqueues) \
+	((uint64_t)(nqueues) * sizeof(struct xfg_sock_ring) + XFG_FWD_HASH_SLOTS * sizeof(struct xfg_fwd_slot))
+
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 #define XFG_HD __host__ __device__ __forceinline__
@@ -623,6 +659,12 @@ XFG_HD uint32_t xfg_fmix32(uint32_t h)
 	h *= 0xc2b2ae35u;
 	h ^= h >> 16;
 	return h;
+}
+
+/* the first slot an ifindex is looked for in (struct xfg_fwd_slot) */
+XFG_HD uint32_t xfg_fwd_hash(uint32_t ifindex)
+{
+	return (ifindex * 0x9e3779b1u) >> 25;
 }
 
 XFG_HD uint32_t xfg_hash_v4(uint32_t k, uint32_t seed)

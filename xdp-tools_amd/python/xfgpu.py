@@ -68,6 +68,7 @@ EXPORTS = [
     "xfg_classify_chain", "xfg_classify_descs_chain", "xfg_classify_descs_chain_timed",
     "xfg_classify_descs_frags_chain", "xfg_classify_descs_frags_chain_timed",
     "xfg_steer_egress", "xfg_steer_frags_egress",
+    "xfg_fib_create", "xfg_fib_free", "xfg_fib_lookup_host", "xfg_forward_egress",
 ]
 CAPTURE_HEAD_ONLY = 1        # XFG_CAPTURE_HEAD_ONLY
 SOCKS_MAX = 1024
@@ -78,6 +79,10 @@ EGRESS_MULTIBUF = 4
 STEER_QUEUES_MAX, STEER_AVAIL_MAX = 64, 256      # XFG_STEER_QUEUES_MAX, XFG_STEER_AVAIL_MAX
 STEER_L4_HASH, STEER_L4_SPORT, STEER_L4_DPORT = 0, 1, 2
 QUEUE_NONE = 0xff            # XFG_QUEUE_NONE
+FIB_NEXTHOPS_MAX, FIB_GROUPS_MAX = 32767, 32768  # XFG_FIB_NEXTHOPS_MAX, XFG_FIB_GROUPS_MAX
+FWD_PORTS_MAX, FWD_REASONS = 63, 9               # XFG_FWD_PORTS_MAX, XFG_FWD_REASONS
+(FWD_OK, FWD_NOT_IP, FWD_BAD_HDR, FWD_TTL, FWD_V6, FWD_NO_ROUTE, FWD_NH_RET, FWD_FRAG,
+ FWD_NO_PORT) = range(9)
 XDP_PKT_CONTD = 1
 XDP_ABORTED, XDP_DROP, XDP_PASS = 0, 1, 2
 CHAIN_PASS = 1 << XDP_PASS   # XFG_CHAIN_PASS
@@ -137,6 +142,72 @@ class Steer(C.Structure):
                 ("fill_addrs", C.c_void_p), ("fill_first", C.c_uint32), ("fill_mask", C.c_uint32),
                 ("count", C.c_uint64), ("counts", C.c_void_p), ("queue_of", C.c_void_p),
                 ("flags", C.c_uint32)]
+
+
+class FibNexthop(C.Structure):
+    """struct xfg_fib_nexthop."""
+    _fields_ = [("ifindex", C.c_uint32), ("mtu", C.c_uint16), ("ret", C.c_uint8),
+                ("dmac", C.c_uint8 * 6), ("smac", C.c_uint8 * 6)]
+
+
+class FibRoute(C.Structure):
+    """struct xfg_fib_route: prefix in host order."""
+    _fields_ = [("prefix", C.c_uint32), ("nexthop", C.c_uint32), ("len", C.c_uint8)]
+
+
+class FwdPort(C.Structure):
+    """struct xfg_fwd_port: one egress port and its TX ring."""
+    _fields_ = [("ifindex", C.c_uint32), ("tx_descs", C.c_void_p), ("tx_first", C.c_uint32),
+                ("tx_mask", C.c_uint32)]
+
+
+class Forward(C.Structure):
+    """struct xfg_forward (xfg_forward_egress)."""
+    _fields_ = [("sz", C.c_size_t), ("umem", C.c_void_p),
+                ("rx_descs", C.c_void_p), ("rx_first", C.c_uint32), ("rx_mask", C.c_uint32),
+                ("fib", C.c_void_p), ("ports", C.POINTER(FwdPort)), ("nports", C.c_uint32),
+                ("stack", SteerQueue),
+                ("fill_addrs", C.c_void_p), ("fill_first", C.c_uint32), ("fill_mask", C.c_uint32),
+                ("count", C.c_uint64), ("counts", C.c_void_p), ("queue_of", C.c_void_p),
+                ("reason_of", C.c_void_p), ("flags", C.c_uint32)]
+
+
+def fib_routes(routes):
+    """A ctypes array of FibRoute from (prefix, len, nexthop) triples (prefix in
+    host order) or an (n, 3) integer array of them."""
+    a = np.asarray(routes, np.int64).reshape(-1, 3)
+    arr = (FibRoute * max(len(a), 1))()
+    v = np.zeros(len(a), np.dtype([("prefix", "<u4"), ("nexthop", "<u4"), ("len", "u1")],
+                                  align=True))
+    v["prefix"], v["len"], v["nexthop"] = a[:, 0], a[:, 1], a[:, 2]
+    assert v.dtype.itemsize == C.sizeof(FibRoute)
+    C.memmove(arr, v.ctypes.data, v.nbytes)
+    return arr
+
+
+def fib_nexthops(nexthops):
+    """A ctypes array of FibNexthop from (ifindex, mtu, ret, dmac, smac) tuples,
+    the MACs six bytes each."""
+    arr = (FibNexthop * max(len(nexthops), 1))()
+    for i, (ifindex, mtu, ret, dmac, smac) in enumerate(nexthops):
+        arr[i] = FibNexthop(ifindex, mtu, ret, (C.c_uint8 * 6)(*bytes(dmac)),
+                            (C.c_uint8 * 6)(*bytes(smac)))
+    return arr
+
+
+def fwd_ports(ports):
+    """A host port table (a ctypes array of FwdPort) from FwdPort values or
+    (ifindex, tx_ptr[, tx_first, tx_mask]) tuples; without the last two the
+    ring is a plain array."""
+    arr = (FwdPort * max(len(ports), 1))()
+    for i, p in enumerate(ports):
+        if isinstance(p, FwdPort):
+            arr[i] = p
+        elif len(p) == 2:
+            arr[i] = FwdPort(p[0], p[1], 0, 0xffffffff)
+        else:
+            arr[i] = FwdPort(*p)
+    return arr
 
 
 def steer_queues(queues):
@@ -293,6 +364,11 @@ def _load():
         "xfg_classify_socks": (C.c_int, [vp, C.c_int, C.POINTER(Socks), vp, vp]),
         "xfg_steer_egress": (C.c_int, [vp, C.c_int, C.POINTER(Steer), vp, vp]),
         "xfg_steer_frags_egress": (C.c_int, [vp, C.c_int, C.POINTER(Steer), vp, vp]),
+        "xfg_fib_create": (C.c_int, [vp, C.c_int, C.POINTER(FibRoute), C.c_uint64,
+                                     C.POINTER(FibNexthop), C.c_uint32, C.POINTER(vp)]),
+        "xfg_fib_free": (None, [vp]),
+        "xfg_fib_lookup_host": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+        "xfg_forward_egress": (C.c_int, [vp, C.c_int, C.POINTER(Forward), vp, vp]),
         "xfg_socks_egress": (C.c_int, [vp, C.c_int, C.POINTER(Socks), C.POINTER(SocksEgress), vp,
                                        vp]),
         "xfg_classify_socks_frags": (C.c_int, [vp, C.c_int, C.POINTER(Socks),
@@ -462,6 +538,42 @@ class DeviceBuffer:
         if self.ptr:
             lib.xfg_dev_free(self.filt.ctx, self.dev, self.ptr)
             self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Fib:
+    """An immutable IPv4 forwarding table (xfg_fib_create): routes as
+    fib_routes() takes them, next hops as fib_nexthops() takes them.  On a
+    host-only context only the host copy is built (lookup() reads it); on a
+    device context the tables are uploaded to device dev once, here."""
+
+    def __init__(self, filt: "Filter", routes, nexthops, dev=0):
+        r = routes if isinstance(routes, C.Array) else fib_routes(routes)
+        h = nexthops if isinstance(nexthops, C.Array) else fib_nexthops(nexthops)
+        self.filt, self.dev, self.ptr = filt, dev, None
+        out = C.c_void_p()
+        _check(lib.xfg_fib_create(filt.ctx, dev, r, len(routes), h, len(nexthops), C.byref(out)),
+               "fib_create")
+        self.ptr = out
+
+    def lookup(self, dst):
+        """The next hop of the longest match of dst (host order), or None."""
+        nh = C.c_uint32()
+        rc = lib.xfg_fib_lookup_host(self.ptr, int(dst), C.byref(nh))
+        if rc == -2:   # -ENOENT
+            return None
+        _check(rc, "fib_lookup_host")
+        return nh.value
+
+    def free(self):
+        if self.ptr and getattr(self.filt, "ctx", None):
+            lib.xfg_fib_free(self.ptr)
+        self.ptr = None
 
     def __del__(self):
         try:
@@ -793,6 +905,27 @@ class Filter:
                   queue_of_ptr, flags)
         _check(lib.xfg_steer_frags_egress(self.ctx, dev, C.byref(s), verdicts_ptr, stream),
                "steer_frags_egress")
+
+    def forward_egress(self, umem_ptr, rx_ptr, count, verdicts_ptr, counts_ptr, fib, ports, stack,
+                       nports=None, fill_ptr=None, rx_first=0, rx_mask=0xffffffff, fill_first=0,
+                       fill_mask=0xffffffff, queue_of_ptr=None, reason_of_ptr=None, flags=0,
+                       dev=0, stream=None):
+        """The PASS frames of an RX descriptor batch to the TX ring of the port
+        a FIB lookup names, their TTL, checksum and MACs rewritten in the UMEM;
+        the PASS frames that are not forwarded to the stack ring; the others'
+        chunks to the fill ring (xfg_forward_egress).  fib: a Fib; ports: a host
+        table from fwd_ports() (or what it takes); stack: a SteerQueue, a
+        (tx_ptr, tx_first, tx_mask) triple or a bare pointer; counts_ptr:
+        nports + 2 + FWD_REASONS u64 on the device.  The port table may be
+        overwritten as soon as this returns."""
+        tab = ports if isinstance(ports, C.Array) else fwd_ports(ports)
+        f = Forward(C.sizeof(Forward), umem_ptr, rx_ptr, rx_first, rx_mask,
+                    fib.ptr if isinstance(fib, Fib) else fib, tab,
+                    len(ports) if nports is None else nports, steer_queues([stack])[0],
+                    fill_ptr, fill_first, fill_mask, count, counts_ptr, queue_of_ptr,
+                    reason_of_ptr, flags)
+        _check(lib.xfg_forward_egress(self.ctx, dev, C.byref(f), verdicts_ptr, stream),
+               "forward_egress")
 
     def classify_socks(self, umem_ptr, socks, verdicts_ptr, nsocks=None, flat_ptr=None, dev=0,
                        stream=None):
