@@ -1,6 +1,7 @@
-"""The forwarded egress call (xfg_forward_egress) as a numpy/Python model, held
-to xdp-forward by citation: xdp_fwd_flags() of xdp-forward/xdp_forward.bpf.c
-(:32-127, ip_decrease_ttl :23-30) over headers/xdp/parsing_helpers.h's
+"""The forwarded egress call (xfg_forward_egress) as a numpy/Python model,
+written from xdp-forward's text and held equal to the program itself, compiled
+for the host, by tests/test_forward_reference.py: xdp_fwd_flags() of
+xdp-forward/xdp_forward.bpf.c (:32-127, ip_decrease_ttl :23-30) over headers/xdp/parsing_helpers.h's
 parse_ethhdr (:100-134, VLAN_MAX_DEPTH 4, :80) and parse_iphdr (:201-233),
 with bpf_fib_lookup (a kernel helper) replaced by a longest-prefix match over a
 route list.  The match here is brute force -- lpm() tries every route;

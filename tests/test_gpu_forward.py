@@ -3,8 +3,11 @@ an RX batch to the TX ring of the egress port a device-resident FIB names,
 their TTL, checksum and MACs rewritten in the UMEM; the PASS frames the program
 would hand to the stack to the stack ring; the others' chunks to the fill ring.
 
-Every comparison is exact against tests/fwdmodel.py (held to xdp-forward by
-citation; tests/test_forward_model.py).  A case's frames are a pool of distinct
+Every comparison is exact against tests/fwdmodel.py, which
+test_forward_reference.py holds equal to the reference's own xdp-forward
+program run on the host (oracle/ref/ref_forward_harness.c) over a corpus and
+100,000 mutated frames; test_gpu_forward_reference.py beside this file takes
+its expected values from that run directly.  A case's frames are a pool of distinct
 frames in a UMEM of random bytes and records that name each at most once;
 every ring, queue_of, reason_of and counts are uploaded as 0xA5 bytes and
 compared whole against a copy with the expected entries written in, and the
@@ -57,19 +60,39 @@ def run_forward(G, f, fib, pool, fid, v, routes, nexthops, ifx, kind="array", ro
     """One call over the records fid (distinct indices into pool) with verdicts
     v over the ports ifx; everything compared with the model.  Returns the
     expected counts."""
-    n, P = len(v), len(ifx)
+    n = len(v)
     assert len(set(fid.tolist())) == n
     umem, paddr, pstart, plens = umem_of_pool(pool, seed)
     addr, lens, start = paddr[fid], plens[fid], pstart[fid]
     want_tx, want_fill, want_counts, want_qof, want_rof, after = M.forward_model(
         pool, fid, addr, lens, v, routes, nexthops, ifx)
+    want_umem = umem.copy()
+    for i in range(n):
+        want_umem[start[i]:start[i] + len(after[i])] = np.frombuffer(after[i], np.uint8)
+    return check_forward(G, f, fib, umem, addr, lens, v, ifx,
+                         (want_tx, want_fill, want_counts, want_qof, want_rof, want_umem), kind=kind, rot=rot,
+                         fill=fill, queue_of=queue_of, reason_of=reason_of)
+
+
+def check_forward(G, f, fib, umem, addr, lens, v, ifx, want, kind="array", rot=0, fill=True, queue_of=True,
+                  reason_of=True, options=True, classify=None):
+    """One call over the records (addr, lens) with verdicts v over the ports
+    ifx; checks counts, every ring, queue_of, reason_of and the UMEM whole
+    against @want = (tx, fill, counts, queue_of, reason_of, umem): the first
+    five as fwdmodel.forward_model returns them, the last the whole UMEM when
+    the call has run, wherever they come from.  @classify(d_u, d_rx, d_v): the
+    verdicts are not uploaded but left by what it launches, the forward call
+    follows with nothing in between, and they must come out as v."""
+    n, P = len(v), len(ifx)
+    want_tx, want_fill, want_counts, want_qof, want_rof, want_umem = want
     rings = Rings(n, kind, rot)
     rx_e, tx_e, fill_e = rings.entries
     rx_h = np.full((max(rx_e, 1), 2), A5, np.uint64)
     rec = np.empty((n, 2), np.uint64)
     rec[:, 0] = addr
-    rec[:, 1] = lens.astype(np.uint64) | (np.where(np.arange(n) % 5 == 4, 1 << 16, 0).astype(np.uint64)
-                                          << np.uint64(32))     # option bits a TX record must not carry
+    rec[:, 1] = lens.astype(np.uint64)
+    if options:     # option bits a TX record must not carry
+        rec[:, 1] |= np.where(np.arange(n) % 5 == 4, 1 << 16, 0).astype(np.uint64) << np.uint64(32)
     rx_h[slots(rings.first[0], n, rings.mask[0])] = rec
     tx_h = np.full((P + 1, max(tx_e, 1), 2), A5, np.uint64)
     fill_h = np.full(max(fill_e, 1), A5, np.uint64)
@@ -83,7 +106,11 @@ def run_forward(G, f, fib, pool, fid, v, routes, nexthops, ifx, kind="array", ro
     try:
         for d, a in zip(bufs, hosts):
             d.upload(a)
-        if n:
+        if classify:
+            d_v.upload(np.zeros(max(n, 16), np.uint8))
+            f.sync()
+            classify(d_u, d_rx, d_v)
+        elif n:
             d_v.upload(np.ascontiguousarray(v))
         q_at = [(d_tx.ptr + q * tx_h[0].nbytes, tx_first[q], rings.mask[1]) for q in range(P + 1)]
         ports = [(ifx[q],) + q_at[q] for q in range(P)]
@@ -94,6 +121,8 @@ def run_forward(G, f, fib, pool, fid, v, routes, nexthops, ifx, kind="array", ro
                          reason_of_ptr=d_rof.ptr if reason_of else None)
         f.sync()
         got = [d.download(np.zeros_like(a)) for d, a in zip(bufs, hosts)]
+        if classify:
+            np.testing.assert_array_equal(d_v.download(np.zeros(max(n, 16), np.uint8))[:n], v)
     finally:
         for b in bufs:
             b.free()
@@ -113,9 +142,6 @@ def run_forward(G, f, fib, pool, fid, v, routes, nexthops, ifx, kind="array", ro
     if fill:
         fill_h[slots(rings.first[2], len(want_fill), rings.mask[2])] = want_fill
     np.testing.assert_array_equal(got_fill, fill_h)
-    want_umem = umem.copy()
-    for i in range(n):
-        want_umem[start[i]:start[i] + len(after[i])] = np.frombuffer(after[i], np.uint8)
     np.testing.assert_array_equal(got_umem, want_umem)
     return want_counts
 

@@ -385,3 +385,86 @@ def run_reference_steer(data, lens, mode, avail, skip_queue=0, stride=0, offsets
         bad = int(np.flatnonzero(~(redirect | (rcs == XDP_PASS)))[0])
         raise RuntimeError(f"reference returned {int(rcs[bad])} for frame {bad}: an avail entry >= nr_cpus?")
     return np.where(redirect, keys, skip_queue).astype(np.uint32), ~redirect
+
+
+# ----------------------------------------------------------------- reference, xdp-forward
+FWD_FULL, FWD_DIRECT = 0, 1                         # ref_forward_harness.c's modes
+# ref_forward_harness.c's stages: where a frame's run ended
+(FWD_ST_EARLY, FWD_ST_NO_ROUTE, FWD_ST_NH_RET, FWD_ST_FRAG, FWD_ST_NO_PORT, FWD_ST_REDIRECT,
+ FWD_ST_V6) = range(7)
+FWD_STAGES = 7
+_ref_forward = None
+
+
+def _ref_forward_path():
+    return os.path.join(REF_DIR, "libref_forward.so")
+
+
+def have_reference_forward() -> bool:
+    """True when the host build of the reference's xdp-forward program is present."""
+    return os.path.exists(_ref_forward_path())
+
+
+def reference_forward():
+    """The host build of the reference's xdp_forward.bpf.c (oracle/ref/)."""
+    global _ref_forward
+    if _ref_forward is None:
+        lib = C.CDLL(_ref_forward_path())
+        lib.ref_forward_run.argtypes = [_u8p, _u64p, C.c_uint32, _u32p, C.c_uint64, C.c_uint32,
+                                        _u32p, C.c_uint32, _u32p, _u8p, C.c_uint32, _u32p, C.c_uint32,
+                                        _u8p, _u32p, _u8p, _u8p, C.c_uint32, _u32p]
+        _ref_forward = lib
+    return _ref_forward
+
+
+def forward_tables(routes, nexthops):
+    """(routes u32[r, 3], nh u32[h, 3], macs u8[h, 12]) as ref_forward_run takes
+    them, from (prefix, len, nexthop) and (ifindex, mtu, ret, dmac, smac) tuples."""
+    r = np.ascontiguousarray(np.asarray(routes, np.int64).reshape(-1, 3), np.uint32)
+    nh = np.ascontiguousarray([[h[0], h[1], h[2]] for h in nexthops], np.uint32).reshape(-1, 3)
+    macs = np.frombuffer(b"".join(bytes(h[3]) + bytes(h[4]) for h in nexthops), np.uint8).reshape(-1, 12)
+    return r, nh, np.ascontiguousarray(macs)
+
+
+def run_reference_forward(data, lens, routes, nexthops, ports, stride=0, offsets=None, mode=FWD_FULL):
+    """Run the reference's xdp_fwd_fib_full (mode FWD_DIRECT: xdp_fwd_fib_direct)
+    with the route list, next hops and xdp_tx_ports ifindex list given, in
+    xfg_forward_egress's terms.  Returns (queue, stage, after, seen): queue[i]
+    the position in ports of the key the program redirected frame i to, len(ports)
+    (the stack ring) where it returned XDP_PASS; stage[i] FWD_ST_*; after u8[n,
+    width] the frames' bytes when the program has run (zeros behind lens[i]);
+    seen u32[n, 3] the family, tot_len and ipv4_dst the lookup was handed
+    (0xffffffff where it was not called).  Any other return code, or a redirect
+    to a key that is no port, raises."""
+    lib = reference_forward()
+    n = len(lens)
+    data = np.ascontiguousarray(data, np.uint8)
+    lens = np.ascontiguousarray(lens, np.uint32)
+    offs = None if offsets is None else np.ascontiguousarray(offsets, np.uint64)
+    r, nh, macs = forward_tables(routes, nexthops)
+    pt = np.ascontiguousarray(ports, np.uint32)
+    width = max(int(lens.max()) if n else 0, 1)
+    rcs = np.zeros(n, np.uint8)
+    keys = np.zeros(n, np.uint32)
+    stages = np.zeros(n, np.uint8)
+    after = np.zeros((n, width), np.uint8)
+    seen = np.zeros((n, 3), np.uint32)
+    if lib.ref_forward_run(ptr(data), ptr(offs, _u64p), stride, ptr(lens, _u32p), n, mode,
+                           ptr(r, _u32p), len(r), ptr(nh, _u32p), ptr(macs), len(nh),
+                           ptr(pt, _u32p), len(pt), ptr(rcs), ptr(keys, _u32p), ptr(stages),
+                           ptr(after), width, ptr(seen, _u32p)):
+        raise RuntimeError("reference run failed (mode, a malformed route, or no arena below 4 GiB)")
+    redirect = rcs == XDP_REDIRECT
+    if not (redirect | (rcs == XDP_PASS)).all():
+        bad = int(np.flatnonzero(~(redirect | (rcs == XDP_PASS)))[0])
+        raise RuntimeError(f"reference returned {int(rcs[bad])} for frame {bad}")
+    if (redirect != (stages == FWD_ST_REDIRECT)).any():
+        raise RuntimeError("reference: XDP_REDIRECT and the redirect stage disagree")
+    queue = np.full(n, len(pt), np.uint32)
+    if redirect.any():
+        order = np.argsort(pt, kind="stable")
+        at = np.minimum(np.searchsorted(pt[order], keys[redirect]), len(pt) - 1)
+        if (pt[order][at] != keys[redirect]).any():
+            raise RuntimeError("reference redirected to a key that is no port")
+        queue[redirect] = order[at]
+    return queue, stages, after, seen
