@@ -905,10 +905,11 @@ int xfg_fib_lookup_host(const xfg_fib *fib, uint32_t dst, uint32_t *nexthop);
  * -- and written for every forwarded one, within those bytes.
  *
  * Limits: IPv4 only (an IPv6 frame goes to the stack ring with XFG_FWD_V6); 63
- * ports; an immutable FIB; single-buffer frames (a multi-buffer batch must not
- * be passed: a continuation record would be parsed as a frame).  Many-socket
- * rounds run over the flat array xfg_classify_socks leaves.  Not covered: the
- * host-memory path, the CLI, the xdp_flowtable programs.
+ * ports; an immutable FIB.  This call takes single-buffer frames (it would
+ * parse a continuation record as a frame); a batch of a socket bound with
+ * XDP_USE_SG goes to xfg_forward_frags_egress below.  Many-socket rounds run
+ * over the flat array xfg_classify_socks leaves.  Not covered: the host-memory
+ * path, the CLI, the xdp_flowtable programs.
  *
  * -EINVAL: everything xfg_steer_egress refuses of the fields the two share,
  * and: fib NULL, of another context or built for another device; nports 0 or
@@ -949,11 +950,69 @@ struct xfg_forward {
 	uint64_t count;             /* < 2^32 */
 	uint64_t *counts;           /* device, (nports + 2 + XFG_FWD_REASONS) x u64 */
 	uint8_t *queue_of, *reason_of;      /* device, count bytes each, or NULL */
-	uint32_t flags;             /* none defined: non-zero is refused */
+	uint32_t flags;             /* xfg_forward_egress: non-zero is refused */
 };
 
 int xfg_forward_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f,
 		       const uint8_t *verdicts, void *stream);
+
+/*
+ * Forwarded egress of multi-buffer packets: every record of a packet follows
+ * its head record's port.  The structure, the program run on a frame, the
+ * FIB, the rewrite, the tables' staging and the stream ordering are
+ * xfg_forward_egress's, bit for bit; what differs is what a record is part of.
+ * An XDP program sees only a packet's first buffer, so the program --
+ * xdp_fwd_fib_full -- runs on bytes [0, len) of the head record, and
+ * XFG_FWD_FRAG compares the header's tot_len, not any record's len.
+ *
+ * Packets are formed exactly as xfg_steer_frags_egress forms them (live, eop
+ * and head as its comment gives them), so one call serves the output of
+ * xfg_classify_descs_frags (count = its counts[1]) and, as a plain array,
+ * sk->flat of xfg_classify_socks_frags.  A packet's record count is not
+ * limited.
+ *
+ * The head decides the whole packet:
+ *   head byte XFG_XDP_PASS, reason XFG_FWD_OK: every live record of the packet
+ *     goes to port q's TX ring, and the head's frame alone is rewritten in the
+ *     UMEM (TTL, check field, MACs, as above);
+ *   head byte XFG_XDP_PASS, any other reason: every live record goes to the
+ *     stack ring, and nothing in the UMEM is written;
+ *   any other head byte: every live record's chunk goes to the fill ring.
+ * The other records' verdict bytes count for liveness only, and no UMEM byte
+ * of a record that is not a PASS head is read or written: a continuation chunk
+ * that happens to hold a routable frame is neither followed nor decremented.
+ *
+ * The k-th live record in record order that takes queue q (a port, or nports:
+ * the stack ring) becomes that ring's entry (tx_first + k) & tx_mask: addr and
+ * len as received, options = the RX record's options & XFG_XDP_PKT_CONTD, so a
+ * packet's records lie adjacent and in order on one ring.  The j-th live
+ * record on the fill side writes fill_addrs[(fill_first + j) & fill_mask] =
+ * addr & ((1 << 48) - 1) (fill_addrs == NULL: none written).  A record that is
+ * not live produces nothing and is counted nowhere.  counts[q] and
+ * counts[nports]: TX records, per record; counts[nports + 1]: the live records
+ * on the fill side; counts[nports + 2 + r]: the PASS packets with reason r, per
+ * packet (only heads are parsed).  queue_of[i] and reason_of[i]: the packet's
+ * queue and the packet's reason for every live record of a PASS packet,
+ * XFG_QUEUE_NONE for every other record, those that are not live included.
+ * The head descriptors of one batch must name distinct frames.
+ *
+ * Nothing depends on timing: a packet whose records lie in several of the
+ * kernel's tiles takes its queue and reason from the tile that parsed its
+ * head, never from a second look at a frame that may have been rewritten.
+ *
+ * flags: XFG_EGRESS_MULTIBUF (implied here) or none; every other bit is
+ * refused.  If every record is an end of packet and no byte is
+ * XFG_VERDICT_NONE, every output byte -- the rings, queue_of, reason_of, the
+ * counts, the UMEM -- equals xfg_forward_egress's.
+ *
+ * -EINVAL: everything xfg_forward_egress refuses, but for XFG_EGRESS_MULTIBUF.
+ * -ENODEV on a host-only context, after these checks; no device pointer is
+ * touched before it.  count == 0: the counts are zeroed and nothing else is
+ * written.  Stream-ordered on @stream, no host synchronisation; ports reaches
+ * the device through the same staging slots.
+ */
+int xfg_forward_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f,
+			     const uint8_t *verdicts, void *stream);
 
 /*
  * Many sockets over one UMEM: one classify and one egress for a whole poll

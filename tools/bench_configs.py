@@ -72,6 +72,12 @@
       records and verdicts; and the same records as single-record packets
       through xfg_steer_egress and xfg_steer_frags_egress (8 rings) -- timed as
       c3st's legs are
+  c3mfw c3m's batch classified by xfg_classify_descs_frags, then forwarded by
+      whole packets (xfg_forward_frags_egress) over 8 ports by c3fw's two FIBs,
+      beside xfg_ring_egress with XFG_EGRESS_MULTIBUF on the same records and
+      verdicts; and the same records as single-record packets through
+      xfg_forward_egress and xfg_forward_frags_egress -- timed as c3fw's legs
+      are, with its rule for the runs after which fewer packets are forwarded
   c3mch c3m's batch, classified by xfg_classify_descs_frags, as the first stage
       of a chain (xfg_classify_descs_frags_chain): half the packets' verdict
       bytes pre-set to PASS, once every other packet and once a contiguous
@@ -858,6 +864,114 @@ def run_c3mst(args):
     print(json.dumps(line), flush=True)
 
 
+def run_c3mfw(args):
+    """c3m's batch classified by xfg_classify_descs_frags, then forwarded by
+    whole packets (xfg_forward_frags_egress) over 8 ports by a 2^20-route FIB
+    and by a default route alone, beside xfg_ring_egress with
+    XFG_EGRESS_MULTIBUF on the same records and verdicts; and the same records
+    with XDP_PKT_CONTD cleared (every record its own packet) through
+    xfg_forward_egress and xfg_forward_frags_egress: the price of the new
+    kernel where the old one could be used.  Legs timed as c3fw's, with its
+    rule for the runs after which fewer frames are forwarded."""
+    import numpy as np
+    import torch
+    import xfgpu as G
+    cm = c3m_workload(args, "c3mfw")
+    w, nrec, entries, first = cm.w, cm.nrec, cm.entries, cm.first
+    f, n = w.f, w.n
+    npass = int(np.count_nonzero(cm.hv == 2))     # PASS packets: three TX records each
+    P = 8
+    ncounts = P + 2 + G.FWD_REASONS
+    d_tx, d_fill, d_c = f.alloc(16 * entries * (P + 1)), f.alloc(8 * entries), f.alloc(8 * ncounts)
+    # the all-end-of-packet batch: the same records, the option words cleared
+    descs = cm.d_descs.download(np.zeros((entries, 2), np.uint64))
+    descs[:, 1] &= np.uint64(0xffffffff)
+    d_eop = f.alloc(descs.nbytes)
+    d_eop.upload(descs)
+    del descs
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    ring = dict(rx_first=first, rx_mask=entries - 1, fill_first=entries - 555, fill_mask=entries - 1)
+    rings = [(d_tx.ptr + 16 * entries * q, entries - 777 + q, entries - 1) for q in range(P + 1)]
+    ports = G.fwd_ports([(10 + q,) + rings[q] for q in range(P)])
+    fibs = {"2p20": c3fw_fib(f, G, 1 << 20, P), "default": c3fw_fib(f, G, 1, P)}
+
+    def forward(call, d_rx, fib):
+        return lambda: call(w.d_umem.ptr, d_rx.ptr, nrec, cm.d_verd.ptr, d_c.ptr, fib, ports, rings[P],
+                            fill_ptr=d_fill.ptr, stream=sp, **ring)
+
+    legs = {"ring_egress_multibuf": lambda: f.ring_egress(
+        cm.d_descs.ptr, nrec, cm.d_verd.ptr, d_c.ptr, tx_ptr=d_tx.ptr, fill_ptr=d_fill.ptr,
+        tx_first=entries - 777, tx_mask=entries - 1, flags=G.EGRESS_MULTIBUF, stream=sp, **ring)}
+    for k, (fib, _) in fibs.items():
+        legs[f"forward_frags_{k}"] = forward(f.forward_frags_egress, cm.d_descs, fib)
+    legs["all_eop_forward_2p20"] = forward(f.forward_egress, d_eop, fibs["2p20"][0])
+    legs["all_eop_forward_frags_2p20"] = forward(f.forward_frags_egress, d_eop, fibs["2p20"][0])
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(2):
+            call()
+        e0.record(stream)
+        for _ in range(args.iters):
+            call()
+        e1.record(stream)
+        e1.synchronize()
+        return e0.elapsed_time(e1) / args.iters
+
+    def reasons(k):
+        c = d_c.download(np.zeros(ncounts, np.uint64)).astype(np.int64)
+        if k.startswith("all_eop"):
+            assert int(c[:P + 2].sum()) == nrec and int(c[P + 2:].sum()) == 3 * npass, c
+        else:
+            # the rings count records, the reasons packets
+            assert int(c[:P + 1].sum()) == 3 * npass and int(c[P + 1]) == nrec - 3 * npass, c
+            assert int(c[P + 2:].sum()) == npass, c
+        return {"ports": c[:P].tolist(), "stack": int(c[P]), "reasons": c[P + 2:].tolist()}
+
+    runs = max(1, args.runs)
+    ms = {k: [] for k in legs}
+    every = {k: [] for k in legs}
+    seen = {}
+    for r in range(runs):      # the legs interleaved
+        for k, call in legs.items():
+            fwd = k != "ring_egress_multibuf"
+            if r == 0 and fwd:
+                call()
+                torch.cuda.synchronize()
+                seen[k] = {"first_call": reasons(k)}
+            t = timed(call)
+            every[k].append(t)
+            if fwd:
+                # every call decrements the forwarded heads' TTL: a run counts
+                # only while the packets forwarded are the first call's
+                last = reasons(k)
+                seen[k].setdefault("forwarded_after_run", []).append(last["reasons"][0])
+                if last != seen[k]["first_call"]:
+                    continue
+            ms[k].append(t)
+    line = {"config": "c3mfw", "program": f.prog_name, "packets": n, "records": nrec,
+            "pass_packets": npass, "ports": P, "ring_entries": entries, "umem_chunk": C3D_CHUNK,
+            "iters": args.iters, "routes": {k: nr for k, (_, nr) in fibs.items()},
+            "setup_s": round(w.setup_s + time.time() - cm.t0, 1)}
+    for k in legs:
+        if not ms[k]:          # no run left the first call's packets forwarded: all runs, marked
+            ms[k] = every[k]
+            seen[k]["no_run_kept_the_first_calls_packets"] = True
+    ref = min(ms["ring_egress_multibuf"])
+    for k in legs:
+        best = min(ms[k])
+        line[k] = {"ms": [round(m, 4) for m in ms[k]], "vs_ring_egress_multibuf": round(best / ref, 2)}
+        line[k].update(seen.get(k, {}))
+    line["table_cost_ms"] = round(min(ms["forward_frags_2p20"]) - min(ms["forward_frags_default"]), 4)
+    line["all_eop_frags_vs_single"] = round(min(ms["all_eop_forward_frags_2p20"]) /
+                                            min(ms["all_eop_forward_2p20"]), 3)
+    for fib, _ in fibs.values():
+        fib.free()
+    f.close()
+    print(json.dumps(line), flush=True)
+
+
 def run_c3mc(args):
     """c3m's batch classified by xfg_classify_descs_frags, then its DROP
     packets captured whole (xfg_capture_descs_frags, snaplen 0), head only,
@@ -1402,6 +1516,8 @@ def run(name, args):
         return run_c3fw(args)
     if name == "c3m":
         return run_c3m(args)
+    if name == "c3mfw":
+        return run_c3mfw(args)
     if name == "c3mc":
         return run_c3mc(args)
     if name == "c3mst":

@@ -62,6 +62,7 @@ int xfg_launch_socks_frags_spread(const uint8_t *pv, const uint32_t *pkt_of, uin
 int xfg_launch_steer(const struct xfg_steer_kargs *a, unsigned grid, void *stream);
 int xfg_launch_steer_frags(const struct xfg_steer_kargs *a, unsigned grid, void *stream);
 int xfg_launch_forward(const struct xfg_fwd_kargs *a, unsigned grid, void *stream);
+int xfg_launch_forward_frags(const struct xfg_fwd_kargs *a, unsigned grid, void *stream);
 int xfg_launch_socks_frags_egress(const struct xfg_socks_frags_egress_kargs *a, unsigned grid,
 				  void *stream);
 int xfg_launch_qt_fold(uint32_t *qt_hits, const uint32_t *trans,
@@ -2947,6 +2948,7 @@ _Static_assert(2 * XFG_FWD_PORTS_MAX <= XFG_FWD_HASH_SLOTS, "a probe meets an em
 
 struct forward_job {
 	const struct xfg_forward *f;
+	int frags;
 	struct xfg_fwd_kargs a;
 };
 
@@ -2978,19 +2980,23 @@ static int forward_go(struct xfg_dev *d, unsigned grid, void *arg)
 	a->queues = (const struct xfg_sock_ring *)d->sk_dev[k];
 	a->hash = (const struct xfg_fwd_slot *)(a->queues + a->nqueues);
 	a->state = d->cstatus;
-	err = xfg_launch_forward(a, grid, d->stream);
+	err = j->frags ? xfg_launch_forward_frags(a, grid, d->stream) : xfg_launch_forward(a, grid, d->stream);
 	return socks_table_done(d, k, err);
 fail:
 	return err;
 }
 
-int xfg_forward_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f, const uint8_t *verdicts,
-		       void *stream)
+/* Both forward calls: the single-buffer one, and with @frags the multi-buffer
+ * one (the same structure, checks and table; XFG_EGRESS_MULTIBUF is then a flag
+ * it takes, and the state has the dead column and the carry column). */
+static int forward_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f, const uint8_t *verdicts,
+			  void *stream, int frags)
 {
+	const uint32_t flags_ok = frags ? XFG_EGRESS_MULTIBUF : 0;
 	int err;
 	if (!ctx || !f || f->sz < sizeof(*f) || !f->fib || f->fib->ctx != ctx || !f->ports ||
-	    !f->nports || f->nports > XFG_FWD_PORTS_MAX || f->flags || f->count > 0xffffffffull ||
-	    !f->counts)
+	    !f->nports || f->nports > XFG_FWD_PORTS_MAX || (f->flags & ~flags_ok) ||
+	    f->count > 0xffffffffull || !f->counts)
 		return -EINVAL;
 	if (ctx->ndev && f->fib->dev != dev)
 		return -EINVAL;
@@ -3019,7 +3025,7 @@ int xfg_forward_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f, const
 	if ((err = dev_check(ctx, dev)))
 		return err;
 	struct forward_job j = {
-		.f = f,
+		.f = f, .frags = frags,
 		.a = {
 			.umem = f->umem, .rx = f->rx_descs, .t24 = f->fib->d_t24, .t8 = f->fib->d_t8,
 			.nh = f->fib->d_nh, .fill = f->fill_addrs, .verdicts = verdicts,
@@ -3032,7 +3038,21 @@ int xfg_forward_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f, const
 	};
 	return scratch_launch(&ctx->dev[dev], stream, f->count ? NULL : f->counts,
 			      ((size_t)f->nports + 2 + XFG_FWD_REASONS) * 8,
-			      XFG_STEER_STATE_WORDS(f->count, f->nports + 1), forward_go, &j);
+			      frags ? XFG_FWD_FRAGS_STATE_WORDS(f->count, f->nports + 1)
+				    : XFG_STEER_STATE_WORDS(f->count, f->nports + 1),
+			      forward_go, &j);
+}
+
+int xfg_forward_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f, const uint8_t *verdicts,
+		       void *stream)
+{
+	return forward_egress(ctx, dev, f, verdicts, stream, 0);
+}
+
+int xfg_forward_frags_egress(xfg_ctx *ctx, int dev, const struct xfg_forward *f, const uint8_t *verdicts,
+			     void *stream)
+{
+	return forward_egress(ctx, dev, f, verdicts, stream, 1);
 }
 
 /* Multi-buffer batches of many sockets (include/xdpfilter_gpu.h), a staged

@@ -2230,5 +2230,6 @@ extern "C" uint64_t xfg_compact_tiles(uint64_t n)
 // header rewritten): the steer partition with another choice of queue
 #include "xfg_fib.h"
 #include "xfg_forward.hip"
+#include "xfg_forward_frags.hip"
 
 #endif   // XFG_PART_COMMON

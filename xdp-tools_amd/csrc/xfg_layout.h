@@ -643,6 +643,15 @@ struct xfg_fwd_kargs {
 #define XFG_FWD_HASH_SLOTS 128u
 #define XFG_FWD_TABLE_BYTES(nqueues) \
 	((uint64_t)(nqueues) * sizeof(struct xfg_sock_ring) + XFG_FWD_HASH_SLOTS * sizeof(struct xfg_fwd_slot))
+/* Forwarded egress of multi-buffer packets (xfg_forward_frags.hip,
+ * xfg_forward_frags_egress()): the same arguments, table and counts; the state
+ * words are those of the steered multi-buffer call -- the K columns and the
+ * column of the records that are not live -- and behind them one more word a
+ * tile: the carry column, flag | queue | reason << 8 of the packet that is open
+ * at the tile's end. */
+#define XFG_FWD_FRAGS_CARRY(n, nqueues) (XFG_STEER_FRAGS_DEAD(n, nqueues) + XFG_STEER_TILES(n))
+#define XFG_FWD_FRAGS_STATE_WORDS(n, nqueues) \
+	((XFG_FWD_FRAGS_CARRY(n, nqueues) + XFG_STEER_TILES(n) + 1) & ~1ull)
 
 
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)

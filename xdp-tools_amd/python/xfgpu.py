@@ -69,6 +69,7 @@ EXPORTS = [
     "xfg_classify_descs_frags_chain", "xfg_classify_descs_frags_chain_timed",
     "xfg_steer_egress", "xfg_steer_frags_egress",
     "xfg_fib_create", "xfg_fib_free", "xfg_fib_lookup_host", "xfg_forward_egress",
+    "xfg_forward_frags_egress",
 ]
 CAPTURE_HEAD_ONLY = 1        # XFG_CAPTURE_HEAD_ONLY
 SOCKS_MAX = 1024
@@ -369,6 +370,7 @@ def _load():
         "xfg_fib_free": (None, [vp]),
         "xfg_fib_lookup_host": (C.c_int, [vp, C.c_uint32, C.POINTER(C.c_uint32)]),
         "xfg_forward_egress": (C.c_int, [vp, C.c_int, C.POINTER(Forward), vp, vp]),
+        "xfg_forward_frags_egress": (C.c_int, [vp, C.c_int, C.POINTER(Forward), vp, vp]),
         "xfg_socks_egress": (C.c_int, [vp, C.c_int, C.POINTER(Socks), C.POINTER(SocksEgress), vp,
                                        vp]),
         "xfg_classify_socks_frags": (C.c_int, [vp, C.c_int, C.POINTER(Socks),
@@ -926,6 +928,25 @@ class Filter:
                     reason_of_ptr, flags)
         _check(lib.xfg_forward_egress(self.ctx, dev, C.byref(f), verdicts_ptr, stream),
                "forward_egress")
+
+    def forward_frags_egress(self, umem_ptr, rx_ptr, count, verdicts_ptr, counts_ptr, fib, ports,
+                             stack, nports=None, fill_ptr=None, rx_first=0, rx_mask=0xffffffff,
+                             fill_first=0, fill_mask=0xffffffff, queue_of_ptr=None,
+                             reason_of_ptr=None, flags=0, dev=0, stream=None):
+        """The same over multi-buffer packets (xfg_forward_frags_egress): every
+        live record of a packet whose head is PASS to the TX ring the program
+        gives the head buffer (a port's, the head rewritten, or the stack
+        ring), every live record of any other packet to the fill ring; a record
+        whose verdict byte is VERDICT_NONE to neither.  Arguments as for
+        forward_egress; flags may carry EGRESS_MULTIBUF."""
+        tab = ports if isinstance(ports, C.Array) else fwd_ports(ports)
+        f = Forward(C.sizeof(Forward), umem_ptr, rx_ptr, rx_first, rx_mask,
+                    fib.ptr if isinstance(fib, Fib) else fib, tab,
+                    len(ports) if nports is None else nports, steer_queues([stack])[0],
+                    fill_ptr, fill_first, fill_mask, count, counts_ptr, queue_of_ptr,
+                    reason_of_ptr, flags)
+        _check(lib.xfg_forward_frags_egress(self.ctx, dev, C.byref(f), verdicts_ptr, stream),
+               "forward_frags_egress")
 
     def classify_socks(self, umem_ptr, socks, verdicts_ptr, nsocks=None, flat_ptr=None, dev=0,
                        stream=None):
